@@ -8,14 +8,22 @@ One process per GPU.  `python3 bench.py --gpus N` spawns its own N ranks (sy11.e
 this one touches the GPU); under torch.distributed.run it takes RANK / LOCAL_RANK / WORLD_SIZE from the env instead.
 Rank 0 prints ONE JSON line.
 
-Besides the headline (`value`, configs[2]) the line carries, all measured after the timed region and never part of `value`:
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, configs[2]); with
+--dump-outputs DIR it also writes what the last timed step computed (rank 0's loss, loss items, model and EMA state; the head
+outputs with --mode fwd) as DIR/<name>.npy, float32, arrays over 4 Mi elements as a fixed seeded sample (dump_outputs).  A dump
+run takes its sums over workgroups in a fixed order with the heuristic tiles (`deterministic` true, `tile_tuner` false in the line),
+so two runs dump the same bits; its `ms_per_step` is that mode's, a plain run's is the atomic, tuned path's.
+
+With --full the line also carries, all measured after the timed region and never part of `value`:
   roofline      the kernel family with the largest share of the step (HIP events around every C-ABI launch of one instrumented
                 step, issued behind a head-start delay so that the GPU never waits for the host between launches), its algorithmic
                 bytes / FLOPs, the HBM traffic of the same family from the rocprofv3 PMC passes (profiles/r04/traffic.json, quoted only when measured on this csrc);
   peaks         measured on this GPU in this run: pure-MFMA loop (sy11_peak_mfma_f16) and a 1 GiB device-to-device copy;
   cpu_baseline  the oracle (CPU restatement of the reference path) on the host cores: 7 threads (the reference's default
                 min(8, ncpu - 1)) and all cores, eval forward and train step;
-  forward_only  configs[1]; extra: the f32 train line and configs[4]'s model (fusion variant, nc = 2) at the same batch / size.
+  forward_only  configs[1]; extra: the f32 train line and configs[4]'s model (fusion variant, nc = 2) at the same batch / size;
+  gradient_exchange  (--gpus N > 1) the all-reduce time the launch stream sees.
+Without --full these fields are null.
 """
 from __future__ import annotations
 
@@ -305,6 +313,69 @@ def family_of(name, meta):
     return name
 
 
+DUMP_ELEMS = 1 << 22                 # per dumped array (16 MB in float32): larger outputs are sampled
+DUMP_BYTES = 64 << 20                # all dumped arrays together
+
+
+def flat_sample(name, tensors, limit=DUMP_ELEMS):
+    """``tensors`` flattened and concatenated in float32; beyond ``limit`` elements a fixed sample of ``limit`` distinct positions
+    (evenly strided, offset seeded by the name and the length), so that two builds (or two runs) dump the same positions."""
+    import zlib
+
+    import numpy as np
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    n = flat.numel()
+    if n > limit:                                        # ``limit`` distinct positions, one per stride of n / limit, seeded offset
+        off = int(np.random.default_rng(zlib.crc32(f"{name}:{n}".encode())).integers(0, n // limit))
+        idx = off + (torch.arange(limit, dtype=torch.float64) * (n / limit)).long()
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``{name: [tensors]}`` as out_dir/<name>.npy (float32, see flat_sample); refuses to exceed DUMP_BYTES in all."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    data = {name: flat_sample(name, ts) for name, ts in arrays.items()}
+    total = sum(v.nbytes for v in data.values())
+    if total > DUMP_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte limit")
+    for name, v in data.items():
+        np.save(out_dir / f"{name}.npy", v)
+    return total
+
+
+def step_outputs(tr, out, mode):
+    """What a caller of the timed path holds after a step: the train step's returned loss and loss items plus the model and EMA
+    state it updated (floating-point entries, state_dict order), or the train-mode head outputs of a forward step."""
+    if mode != "train":
+        return {"head_outputs": list(out)}
+    loss, items = out
+    arrays = {"loss": [loss], "loss_items": [items],
+              "model_state": [v for v in tr.model.state_dict().values() if v.dtype.is_floating_point]}
+    if tr.ema:
+        arrays["ema_state"] = [v for v in tr.ema.ema.state_dict().values() if v.dtype.is_floating_point]
+    return arrays
+
+
+def make_workload(a, dev, rank, model_yaml, nc, dtype, with_producer, ws=1):
+    """The trainer, resident inputs and labels of one rank (the caller seeds torch first: trainer.py:107)."""
+    from sy11.data.spectrogram import SpectrogramProducer
+    from sy11.engine.trainer import DetectionTrainer
+    from sy11.nn.tasks import DetectionModel
+    model = DetectionModel(model_yaml, nc=nc, verbose=False)
+    producer = SpectrogramProducer(dev, n_frames=a.imgsz, n_mel=a.imgsz) if with_producer else None
+    tr = DetectionTrainer(model, batch_size=a.batch, device=dev, overrides={"amp": dtype == "f16"}, world_size=ws,
+                          producer=producer, graphs=not a.no_graphs)
+    labels = synthetic_labels(a.batch, 100 + rank, dev, nc=nc)
+    if producer is not None:
+        data = {"iq": synthetic_iq(a.batch, producer.n_samples, 1 + rank, dev)}
+    else:
+        data = {"img": torch.rand(a.batch, 3, a.imgsz, a.imgsz, device=dev)}
+    return tr, data, labels
+
+
 def timed_steps(step, fence, steps, warmup):
     for _ in range(warmup):
         step()
@@ -316,7 +387,7 @@ def timed_steps(step, fence, steps, warmup):
     return time.perf_counter() - t0
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -328,13 +399,21 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=["f16", "f32"])
     ap.add_argument("--mode", default="train", choices=["train", "fwd"])
     ap.add_argument("--no-stft", action="store_true", help="feed resident (B,3,H,W) images instead of IQ")
+    ap.add_argument("--full", action="store_true", help="after the headline also run the reporting legs (roofline, peaks, forward-only, "
+                    "extras, CPU baseline, gradient exchange); the --no-* options below drop single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-fwd-leg", action="store_true", help="skip the forward-only (configs[1]) leg reported next to the headline")
     ap.add_argument("--no-extras", action="store_true", help="skip the f32 train line and the configs[4] model line")
     ap.add_argument("--no-graphs", action="store_true", help="launch every kernel individually instead of hipGraph replay")
     ap.add_argument("--leg", default="", choices=["", "predict_val"], help="run ONE reporting leg only and print its JSON (for rocprofv3 profiles of that leg)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` without a launcher: spawn one CHILD per GPU (engine/trainer.py:170-207, utils/dist.py:25-66).
@@ -356,9 +435,7 @@ def main():
         os.write(json_fd, (json.dumps(obj) + "\n").encode())
 
     from sy11 import _lib
-    from sy11.data.spectrogram import SpectrogramProducer
     from sy11.engine import ddp
-    from sy11.engine.trainer import DetectionTrainer
     from sy11.nn.tasks import DetectionModel
 
     rank, local, world = ddp.setup_process_group(os.environ.get("SY11_DDP_BACKEND"))
@@ -369,18 +446,22 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     torch.manual_seed(0 + 1 + rank)                        # trainer.py:107 init_seeds(seed + 1 + RANK)
+    if a.dump_outputs:
+        # a dump is compared run against run and build against build, so every step before it must compute the same bits.  The
+        # default mode adds workgroup partial sums with atomics in whatever order they land, and the measuring tile tuner may pick
+        # other tiles (other summation orders) in another process: from identical weights two such runs already produce filter
+        # gradients that differ far beyond rounding, and training amplifies it ("Reproducible dumps").  A dump run
+        # therefore runs the ordered-reduction mode (`deterministic`, csrc/det.h) with the heuristic tiles (the tuner does not
+        # measure in that mode): the same kernels' ordered variants, slower than a plain run (+3.8 %).  The result
+        # line says so in `deterministic` and `tile_tuner`; a plain run keeps atomic sums and the measuring tuner.
+        from sy11.utils.torch_utils import set_deterministic
+        set_deterministic(True)
+        if rank == 0:
+            print("[bench] --dump-outputs: ordered reductions, heuristic tiles (reproducible dump; slower than a plain run)",
+                  file=sys.stderr, flush=True)
 
     def make(model_yaml, nc, dtype, with_producer, ws=1):
-        model = DetectionModel(model_yaml, nc=nc, verbose=False)
-        producer = SpectrogramProducer(dev, n_frames=a.imgsz, n_mel=a.imgsz) if with_producer else None
-        tr = DetectionTrainer(model, batch_size=a.batch, device=dev, overrides={"amp": dtype == "f16"}, world_size=ws,
-                              producer=producer, graphs=not a.no_graphs)
-        labels = synthetic_labels(a.batch, 100 + rank, dev, nc=nc)
-        if producer is not None:
-            data = {"iq": synthetic_iq(a.batch, producer.n_samples, 1 + rank, dev)}
-        else:
-            data = {"img": torch.rand(a.batch, 3, a.imgsz, a.imgsz, device=dev)}
-        return tr, data, labels
+        return make_workload(a, dev, rank, model_yaml, nc, dtype, with_producer, ws)
 
     if a.leg == "predict_val":                              # the predict / val side alone: fused eval forward + decode + batched NMS
         from sy11.engine import enable_graphs
@@ -405,14 +486,17 @@ def main():
         return
 
     tr, data, labels = make(a.model, a.nc, a.dtype, not a.no_stft, world)
+    last = [None]                                           # what the latest step returned (--dump-outputs)
 
     def step():
         batch = {**data, **labels}
         if a.mode == "train":
-            return tr.train_step(batch)
+            last[0] = tr.train_step(batch)
+            return last[0]
         with torch.no_grad():
             tr.model.train()
-            return tr.model(tr.preprocess_batch(batch)["img"])
+            last[0] = tr.model(tr.preprocess_batch(batch)["img"])
+            return last[0]
 
     def fence():
         torch.cuda.synchronize()
@@ -428,6 +512,9 @@ def main():
     dt = timed_steps(step, fence, a.steps, a.warmup)
     if rank == 0:
         print(f"[bench] headline: {a.steps} steps, {dt / a.steps * 1e3:.2f} ms/step", file=sys.stderr, flush=True)
+    if rank == 0 and a.dump_outputs:                        # before any reporting leg steps or fuses the model
+        nbytes = dump_outputs(a.dump_outputs, step_outputs(tr, last[0], a.mode))
+        print(f"[bench] outputs of the last timed step: {nbytes / 1e6:.1f} MB in {a.dump_outputs}", file=sys.stderr, flush=True)
     if world > 1:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -435,7 +522,7 @@ def main():
     ms = dt / a.steps * 1e3
     value = a.batch * world * a.steps / dt
     exposed = None
-    if world > 1:
+    if world > 1 and a.full:
         # the gradient exchange as the launch stream sees it: events around the hook's collective(s) (the stream-side wait for RCCL
         # included) over 5 more steps — what of the all-reduce is NOT hidden behind compute
         from sy11.engine import module_post_backward
@@ -456,7 +543,7 @@ def main():
     train_gflop = 3 * fwd_gflop - 0.177 if "fusion" in a.model else TRAIN_GFLOP_PER_IMG
 
     fwd_only = None
-    if rank == 0 and world == 1 and a.mode == "train" and not a.no_fwd_leg:
+    if a.full and rank == 0 and world == 1 and a.mode == "train" and not a.no_fwd_leg:
         # configs[1] of BASELINE.json, reported next to the headline (never part of `value`): forward only, batch statistics,
         # resident spectrogram tensors, the same captured graph machinery
         img = tr.preprocess_batch({**data, **labels})["img"].clone()
@@ -479,9 +566,9 @@ def main():
                     "conv_roofline_frac": round(a.batch / fdt * fwd_gflop / 1e3 / PEAK_TFLOPS[a.dtype], 4)}
 
     roof = None
-    if world > 1 and not a.no_roofline:
+    if world > 1 and a.full and not a.no_roofline:
         step()                                                  # every rank takes the extra step: its gradient all-reduce must be matched
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         # one instrumented step: every C-ABI launch bracketed by events on the launch stream.  The launches are issued behind a
         # ~60 ms head-start delay on the same stream, so the GPU works through an already filled queue: an event pair then spans
         # the kernel(s) of the call, not the host's launch latency (r01: eager event timing read 9.8 ms for a family that takes
@@ -592,7 +679,7 @@ def main():
                           f"minus half the span of an empty event pair ({pair_ms * 1e3:.1f} us); every kernel on ONE stream for this "
                           "step (the headline run overlaps the filter gradients on a second stream: each kernel slower, the step faster)"}
 
-    peaks = measured_peaks(dev) if (rank == 0 and not a.no_roofline) else None
+    peaks = measured_peaks(dev) if (a.full and rank == 0 and not a.no_roofline) else None
 
     if fwd_only is not None:
         # the deployed forward: BatchNorm folded into the convs (model.fuse()), eval mode, Detect decode included.  Last thing
@@ -625,7 +712,7 @@ def main():
             fwd_only["predict_val"] = {"error": repr(e)}
 
     extra = None
-    if rank == 0 and world == 1 and a.mode == "train" and not a.no_extras and a.model == "yolo11s.yaml":
+    if a.full and rank == 0 and world == 1 and a.mode == "train" and not a.no_extras and a.model == "yolo11s.yaml":
         del tr
         torch.cuda.empty_cache()
         extra = {}
@@ -643,7 +730,7 @@ def main():
             torch.cuda.empty_cache()
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -653,7 +740,8 @@ def main():
             else "spectrogram-images/sec (forward only) YOLOv11-s 640², bs=64",
             "value": round(value, 2), "unit": "spectrogram-images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": a.dtype, "data": "synthetic",
+            "dtype": a.dtype, "data": "synthetic", "deterministic": bool(_lib.get_option("deterministic")),
+            "tile_tuner": bool(_lib.get_option("tune")),
             "config": {"workload": ("configs[2]: YOLOv11-s train fwd+bwd (+clip, SGD-nesterov, EMA) from synthetic IQ through the "
                                     "HIP STFT/log-mel producer" if a.mode == "train" and not a.no_stft else
                                     "configs[1]: YOLOv11-s forward" if a.mode == "fwd" else

@@ -75,7 +75,7 @@ def test_bench_two_ranks_prints_exactly_one_json_line(tmp_path):
     env = dict(os.environ, SY11_DDP_BACKEND="gloo", SY11_FORCE_DEVICE="0", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "4", "--imgsz", "256",
-                        "--no-stft", "--no-cpu-baseline", "--no-extras", "--no-fwd-leg"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-stft", "--full", "--no-cpu-baseline", "--no-extras", "--no-fwd-leg"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
     assert len(lines) == 1, r.stdout[:2000]
