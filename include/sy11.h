@@ -395,6 +395,22 @@ int sy11_image_mosaic_warp(int32_t dtype, int32_t n_tiles, const uint8_t* const*
                            const uint8_t* hsv_lut, int32_t flip_ud, int32_t flip_lr, int32_t fill,
                            int32_t reverse_c, int32_t chw, void* dst, void* stream);
 
+/* MixUp (data/augment.py: BaseMixTransform.__call__ :386-407, MixUp.get_indexes :919, MixUp._mix_transform :944-949,
+ * placed by v8_transforms :2310-2342 after Mosaic + RandomPerspective and before RandomHSV / RandomFlip) folded into
+ * the same single launch: TWO geometry recipes, each as in sy11_image_mosaic_warp (n_tiles, tile_src, tile_geom,
+ * canvas_h/w, minv or NULL), both producing H x W.  Every output pixel samples recipe a (the sample) and recipe b (the
+ * partner) and blends per channel as numpy does in (img * r + img2 * (1 - r)).astype(np.uint8): two float64 products
+ * and one float64 sum, each rounded on its own (never an fma), then truncation.  r and one_minus_r are BOTH passed,
+ * formed by the host in float64, finite and in [0 1].  Then the shared tail of sy11_image_mosaic_warp: hsv_lut, the
+ * two flips (of the blended image), fill (the border of both canvases and warps), reverse_c, chw, dtype.
+ * Every argument check of sy11_image_mosaic_warp applies to each recipe; nothing is launched on an error.          */
+int sy11_image_mixup_warp(int32_t dtype, int32_t n_tiles_a, const uint8_t* const* tile_src_a, const int32_t* tile_geom_a,
+                          int32_t canvas_h_a, int32_t canvas_w_a, const double* minv_a, int32_t n_tiles_b,
+                          const uint8_t* const* tile_src_b, const int32_t* tile_geom_b, int32_t canvas_h_b,
+                          int32_t canvas_w_b, const double* minv_b, double r, double one_minus_r, int32_t H, int32_t W,
+                          const uint8_t* hsv_lut, int32_t flip_ud, int32_t flip_lr, int32_t fill,
+                          int32_t reverse_c, int32_t chw, void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

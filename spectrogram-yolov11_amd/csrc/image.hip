@@ -153,19 +153,40 @@ struct WarpTile {
   const uint8_t* src;
   int h, w, x1, y1, x2, y2, padw, padh;
 };
-struct WarpArgs {
+// The geometry half of a recipe: which source pixels make output pixel (x, y).  sy11_image_mosaic_warp carries one,
+// sy11_image_mixup_warp two (the sample and its MixUp partner).
+struct WarpGeom {
   WarpTile tile[4];
   double m[6];
+  int n_tiles, canvas_h, canvas_w, has_warp;
+};
+// The shared tail of both entries: HSV tables, flips, fill, layout.
+struct WarpTail {
   void* dst;
-  int n_tiles, canvas_h, canvas_w, has_warp, H, W, has_hsv, flip_ud, flip_lr, fill, reverse_c, chw;
+  int H, W, has_hsv, flip_ud, flip_lr, fill, reverse_c, chw;
   unsigned lut[192];   // 3 x 256 bytes: hue, sat, val
 };
+struct WarpArgs {
+  WarpGeom g;
+  WarpTail t;
+};
+struct MixArgs {
+  WarpGeom ga, gb;
+  double ra, rb;       // r and 1 - r, both formed by the host in float64
+  WarpTail t;
+};
+// Kernel arguments travel in the kernarg segment (at most 4 KB): two recipes + the 768-byte LUT must stay well inside it.
+// MixArgs is how the host packs them; the kernel takes its five members as separate by-value parameters (the same bytes
+// in the same segment), because the compiler copies a single 1272-byte by-value struct to scratch instead of reading
+// it through scalar loads.
+static_assert(sizeof(WarpGeom) == 224 && sizeof(WarpTail) == 808, "image.hip: recipe layout changed");
+static_assert(sizeof(WarpArgs) == 1032 && sizeof(MixArgs) == 1272 && sizeof(MixArgs) <= 4096, "image.hip: kernel argument size");
 
 __device__ __forceinline__ double nofma(double x) { asm volatile("" : "+v"(x)); return x; }
 __device__ __forceinline__ float nofma(float x) { asm volatile("" : "+v"(x)); return x; }
 
-__device__ __forceinline__ void canvas_fetch(const WarpArgs& a, int cx, int cy, int* v) {
-  v[0] = v[1] = v[2] = a.fill;
+__device__ __forceinline__ void canvas_fetch(const WarpGeom& a, int fill, int cx, int cy, int* v) {
+  v[0] = v[1] = v[2] = fill;
   if ((unsigned)cx >= (unsigned)a.canvas_w || (unsigned)cy >= (unsigned)a.canvas_h) return;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -179,18 +200,8 @@ __device__ __forceinline__ void canvas_fetch(const WarpArgs& a, int cx, int cy, 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void mosaic_warp_kernel(const WarpArgs a) {
-  __shared__ unsigned lut32[192];
-  if (a.has_hsv) {
-    if (threadIdx.x < 192) lut32[threadIdx.x] = a.lut[threadIdx.x];
-    __syncthreads();
-  }
-  const uint8_t* lut = (const uint8_t*)lut32;
-  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
-  if (X >= a.W) return;
-  const int wx = a.flip_lr ? a.W - 1 - X : X, wy = a.flip_ud ? a.H - 1 - Y : Y;
-  int v[3];
+// Output pixel (wx, wy) (flips already undone) of one recipe -> v[3] (source channel order).
+__device__ __forceinline__ void recipe_sample(const WarpGeom& a, int fill, int wx, int wy, int* v) {
   if (a.has_warp) {
     const int adelta = __double2int_rn(a.m[0] * (double)wx * 1024.0), bdelta = __double2int_rn(a.m[3] * (double)wx * 1024.0);
     const int X0 = __double2int_rn((nofma(a.m[1] * (double)wy) + a.m[2]) * 1024.0) + 16;
@@ -202,18 +213,23 @@ __global__ __launch_bounds__(256) void mosaic_warp_kernel(const WarpArgs a) {
     const int fx = Xf & 31, fy = Yf & 31;
     const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
     int t00[3], t01[3], t10[3], t11[3];
-    canvas_fetch(a, sx, sy, t00);
-    canvas_fetch(a, sx + 1, sy, t01);
-    canvas_fetch(a, sx, sy + 1, t10);
-    canvas_fetch(a, sx + 1, sy + 1, t11);
+    canvas_fetch(a, fill, sx, sy, t00);
+    canvas_fetch(a, fill, sx + 1, sy, t01);
+    canvas_fetch(a, fill, sx, sy + 1, t10);
+    canvas_fetch(a, fill, sx + 1, sy + 1, t11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int r = (t00[c] * w00 + t01[c] * w01 + t10[c] * w10 + t11[c] * w11 + 16384) >> 15;
       v[c] = r < 0 ? 0 : (r > 255 ? 255 : r);
     }
   } else {
-    canvas_fetch(a, wx, wy, v);
+    canvas_fetch(a, fill, wx, wy, v);
   }
+}
+
+// RandomHSV on one pixel, the channel swap and the store in dst's layout / dtype: the second half of both kernels.
+template <typename T>
+__device__ __forceinline__ void finish_pixel(const WarpTail& a, const uint8_t* lut, int X, int Y, int* v) {
   if (a.has_hsv) {
     const int b = v[0], g = v[1], r = v[2];
     const int vmax = max(max(b, g), r), vmin = min(min(b, g), r), diff = vmax - vmin;
@@ -271,6 +287,46 @@ __global__ __launch_bounds__(256) void mosaic_warp_kernel(const WarpArgs a) {
       else d[((long)Y * a.W + X) * 3 + c] = o;
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mosaic_warp_kernel(const WarpArgs a) {
+  __shared__ unsigned lut32[192];
+  if (a.t.has_hsv) {
+    if (threadIdx.x < 192) lut32[threadIdx.x] = a.t.lut[threadIdx.x];
+    __syncthreads();
+  }
+  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
+  if (X >= a.t.W) return;
+  const int wx = a.t.flip_lr ? a.t.W - 1 - X : X, wy = a.t.flip_ud ? a.t.H - 1 - Y : Y;
+  int v[3];
+  recipe_sample(a.g, a.t.fill, wx, wy, v);
+  finish_pixel<T>(a.t, (const uint8_t*)lut32, X, Y, v);
+}
+
+// MixUp._mix_transform (data/augment.py:944-949) between the geometry and the colour step: both recipes are sampled at the
+// same output pixel and blended as numpy does — (img * r + img2 * (1 - r)).astype(np.uint8): two float64 products and one
+// float64 sum, each rounded on its own, then truncation.  -ffp-contract=fast would fuse a product into the sum, so the
+// products pass through nofma.  astype(uint8) keeps the low byte of the truncated integer (only reachable when the caller's
+// weights sum to more than 1; for r + (1 - r) the sum stays below 256).
+template <typename T>
+__global__ __launch_bounds__(256) void mixup_warp_kernel(const WarpGeom ga, const WarpGeom gb, const double ra, const double rb,
+                                                         const WarpTail t) {
+  __shared__ unsigned lut32[192];
+  if (t.has_hsv) {
+    if (threadIdx.x < 192) lut32[threadIdx.x] = t.lut[threadIdx.x];
+    __syncthreads();
+  }
+  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
+  if (X >= t.W) return;
+  const int wx = t.flip_lr ? t.W - 1 - X : X, wy = t.flip_ud ? t.H - 1 - Y : Y;
+  int v[3], u[3];
+  recipe_sample(ga, t.fill, wx, wy, v);
+  recipe_sample(gb, t.fill, wx, wy, u);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    v[c] = (int)__dadd_rn(nofma(__dmul_rn((double)v[c], ra)), nofma(__dmul_rn((double)u[c], rb))) & 255;
+  finish_pixel<T>(t, (const uint8_t*)lut32, X, Y, v);
 }
 
 }  // namespace
@@ -338,34 +394,49 @@ extern "C" int sy11_image_letterbox(int32_t dtype, int32_t sh, int32_t sw, int32
   return SY11_OK;
 }
 
-extern "C" int sy11_image_mosaic_warp(int32_t dtype, int32_t n_tiles, const uint8_t* const* tile_src, const int32_t* tile_geom,
-                                      int32_t canvas_h, int32_t canvas_w, const double* minv, int32_t H, int32_t W,
-                                      const uint8_t* hsv_lut, int32_t flip_ud, int32_t flip_lr, int32_t fill,
-                                      int32_t reverse_c, int32_t chw, void* dst, void* stream) {
-  SY11_REQUIRE(dtype_ok(dtype) || dtype == SY11_U8, "image_mosaic_warp: bad dtype %d", dtype);
-  SY11_REQUIRE(n_tiles >= 0 && n_tiles <= 4 && (n_tiles == 0 || (tile_src && tile_geom)), "image_mosaic_warp: 0..4 tiles");
-  SY11_REQUIRE(canvas_h > 0 && canvas_w > 0 && H > 0 && W > 0 && H <= 65535 && dst, "image_mosaic_warp: bad shape");
-  SY11_REQUIRE(minv || (H == canvas_h && W == canvas_w), "image_mosaic_warp: without a warp the output is the canvas (%d x %d)", canvas_h, canvas_w);
-  SY11_REQUIRE(fill >= 0 && fill <= 255, "image_mosaic_warp: fill must be a byte");
-  WarpArgs a;
+// Argument checks and packing of one geometry recipe (`who` names the entry, and the side for the two-recipe one).
+static int pack_geom(const char* who, int n_tiles, const uint8_t* const* tile_src, const int32_t* tile_geom, int canvas_h,
+                     int canvas_w, const double* minv, int H, int W, WarpGeom& a) {
+  SY11_REQUIRE(n_tiles >= 0 && n_tiles <= 4 && (n_tiles == 0 || (tile_src && tile_geom)), "%s: 0..4 tiles", who);
+  SY11_REQUIRE(canvas_h > 0 && canvas_w > 0, "%s: bad shape", who);
+  SY11_REQUIRE(minv || (H == canvas_h && W == canvas_w), "%s: without a warp the output is the canvas (%d x %d)", who, canvas_h, canvas_w);
   for (int t = 0; t < 4; ++t) a.tile[t] = WarpTile{nullptr, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int t = 0; t < n_tiles; ++t) {
     const int32_t* g = tile_geom + 8 * t;
     WarpTile k{tile_src[t], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7]};
-    SY11_REQUIRE(k.src && k.h > 0 && k.w > 0, "image_mosaic_warp: tile %d has no pixels", t);
+    SY11_REQUIRE(k.src && k.h > 0 && k.w > 0, "%s: tile %d has no pixels", who, t);
     SY11_REQUIRE(k.x1 >= 0 && k.y1 >= 0 && k.x2 <= canvas_w && k.y2 <= canvas_h && k.x1 <= k.x2 && k.y1 <= k.y2,
-                 "image_mosaic_warp: tile %d region [%d,%d)x[%d,%d) leaves the %d x %d canvas", t, k.x1, k.x2, k.y1, k.y2, canvas_w, canvas_h);
+                 "%s: tile %d region [%d,%d)x[%d,%d) leaves the %d x %d canvas", who, t, k.x1, k.x2, k.y1, k.y2, canvas_w, canvas_h);
     SY11_REQUIRE(k.x1 - k.padw >= 0 && k.x2 - k.padw <= k.w && k.y1 - k.padh >= 0 && k.y2 - k.padh <= k.h,
-                 "image_mosaic_warp: tile %d region reads outside its %d x %d source", t, k.h, k.w);
+                 "%s: tile %d region reads outside its %d x %d source", who, t, k.h, k.w);
     a.tile[t] = k;
   }
-  a.n_tiles = n_tiles; a.canvas_h = canvas_h; a.canvas_w = canvas_w; a.H = H; a.W = W; a.dst = dst;
+  a.n_tiles = n_tiles; a.canvas_h = canvas_h; a.canvas_w = canvas_w;
   a.has_warp = minv ? 1 : 0;
   for (int i = 0; i < 6; ++i) a.m[i] = minv ? minv[i] : 0.0;
+  return SY11_OK;
+}
+
+static int pack_tail(const char* who, int dtype, int H, int W, const uint8_t* hsv_lut, int flip_ud, int flip_lr, int fill,
+                     int reverse_c, int chw, void* dst, WarpTail& a) {
+  SY11_REQUIRE(dtype_ok(dtype) || dtype == SY11_U8, "%s: bad dtype %d", who, dtype);
+  SY11_REQUIRE(H > 0 && W > 0 && H <= 65535 && dst, "%s: bad shape", who);
+  SY11_REQUIRE(fill >= 0 && fill <= 255, "%s: fill must be a byte", who);
+  a.dst = dst; a.H = H; a.W = W;
   a.has_hsv = hsv_lut ? 1 : 0;
   if (hsv_lut) memcpy(a.lut, hsv_lut, 768);
   else memset(a.lut, 0, 768);
   a.flip_ud = flip_ud; a.flip_lr = flip_lr; a.fill = fill; a.reverse_c = reverse_c; a.chw = chw;
+  return SY11_OK;
+}
+
+extern "C" int sy11_image_mosaic_warp(int32_t dtype, int32_t n_tiles, const uint8_t* const* tile_src, const int32_t* tile_geom,
+                                      int32_t canvas_h, int32_t canvas_w, const double* minv, int32_t H, int32_t W,
+                                      const uint8_t* hsv_lut, int32_t flip_ud, int32_t flip_lr, int32_t fill,
+                                      int32_t reverse_c, int32_t chw, void* dst, void* stream) {
+  WarpArgs a;
+  if (int rc = pack_tail("image_mosaic_warp", dtype, H, W, hsv_lut, flip_ud, flip_lr, fill, reverse_c, chw, dst, a.t)) return rc;
+  if (int rc = pack_geom("image_mosaic_warp", n_tiles, tile_src, tile_geom, canvas_h, canvas_w, minv, H, W, a.g)) return rc;
   const dim3 grid(cdiv(W, 256), H);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == SY11_U8) mosaic_warp_kernel<uint8_t><<<grid, 256, 0, s>>>(a);
@@ -373,5 +444,31 @@ extern "C" int sy11_image_mosaic_warp(int32_t dtype, int32_t n_tiles, const uint
   else if (dtype == SY11_F16) mosaic_warp_kernel<_Float16><<<grid, 256, 0, s>>>(a);
   else mosaic_warp_kernel<__bf16><<<grid, 256, 0, s>>>(a);
   SY11_LAUNCH_CHECK("image_mosaic_warp");
+  return SY11_OK;
+}
+
+extern "C" int sy11_image_mixup_warp(int32_t dtype, int32_t n_tiles_a, const uint8_t* const* tile_src_a, const int32_t* tile_geom_a,
+                                     int32_t canvas_h_a, int32_t canvas_w_a, const double* minv_a, int32_t n_tiles_b,
+                                     const uint8_t* const* tile_src_b, const int32_t* tile_geom_b, int32_t canvas_h_b,
+                                     int32_t canvas_w_b, const double* minv_b, double r, double one_minus_r, int32_t H, int32_t W,
+                                     const uint8_t* hsv_lut, int32_t flip_ud, int32_t flip_lr, int32_t fill,
+                                     int32_t reverse_c, int32_t chw, void* dst, void* stream) {
+  MixArgs a;
+  if (int rc = pack_tail("image_mixup_warp", dtype, H, W, hsv_lut, flip_ud, flip_lr, fill, reverse_c, chw, dst, a.t)) return rc;
+  // each side must produce the H x W of dst: pack_geom checks the canvas of an un-warped side against it, a warped side
+  // takes its output size from the call
+  if (int rc = pack_geom("image_mixup_warp (sample)", n_tiles_a, tile_src_a, tile_geom_a, canvas_h_a, canvas_w_a, minv_a, H, W, a.ga)) return rc;
+  if (int rc = pack_geom("image_mixup_warp (partner)", n_tiles_b, tile_src_b, tile_geom_b, canvas_h_b, canvas_w_b, minv_b, H, W, a.gb)) return rc;
+  // NaN fails both comparisons
+  SY11_REQUIRE(r >= 0.0 && r <= 1.0 && one_minus_r >= 0.0 && one_minus_r <= 1.0,
+               "image_mixup_warp: blend weights must be finite and in [0, 1] (got %g and %g)", r, one_minus_r);
+  a.ra = r; a.rb = one_minus_r;
+  const dim3 grid(cdiv(W, 256), H);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == SY11_U8) mixup_warp_kernel<uint8_t><<<grid, 256, 0, s>>>(a.ga, a.gb, a.ra, a.rb, a.t);
+  else if (dtype == SY11_F32) mixup_warp_kernel<float><<<grid, 256, 0, s>>>(a.ga, a.gb, a.ra, a.rb, a.t);
+  else if (dtype == SY11_F16) mixup_warp_kernel<_Float16><<<grid, 256, 0, s>>>(a.ga, a.gb, a.ra, a.rb, a.t);
+  else mixup_warp_kernel<__bf16><<<grid, 256, 0, s>>>(a.ga, a.gb, a.ra, a.rb, a.t);
+  SY11_LAUNCH_CHECK("image_mixup_warp");
   return SY11_OK;
 }

@@ -99,6 +99,8 @@ SIGNATURES = {
     "sy11_image_resize_bilinear": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "sy11_image_letterbox": [_i32] * 12 + [_vp, _vp, _vp],
     "sy11_image_mosaic_warp": [_i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "sy11_image_mixup_warp": [_i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _f64, _f64, _i32, _i32, _vp, _i32, _i32,
+                              _i32, _i32, _i32, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],

@@ -231,6 +231,11 @@ class DeviceImage:
     ONE kernel launch (sy11_image_mosaic_warp), directly into the batch slot if one is given.  Steps that cannot be
     folded into the single pass (a second warp, a warp after HSV / flips) render to a temporary first, so any order of
     transforms still gives the sequential result.
+
+    MixUp adds one optional field: ``partner``, the geometry half of a second recipe (tiles, canvas, inverted map, the
+    same output size), and ``mix_r``, the weight of this image in the blend.  The blend sits between the geometry and
+    the colour step, so HSV tables and flips recorded after ``mix`` still fold, and ``render`` stays one launch
+    (sy11_image_mixup_warp).
     """
 
     def __init__(self, tiles, canvas_hw, fill=114):
@@ -244,6 +249,8 @@ class DeviceImage:
         self.flip_lr = False
         self.was_numpy = False
         self.final_reverse_c = False          # set by Format(defer=True): the channel flip of _format_img
+        self.partner = None                   # MixUp: a DeviceImage used for its geometry only (tiles, canvas_hw, minv, out_hw)
+        self.mix_r = None                     # ... and the float64 weight r of THIS image: out = trunc(self * r + partner * (1 - r))
 
     # -- construction
     @classmethod
@@ -278,7 +285,7 @@ class DeviceImage:
 
     @property
     def pending(self):
-        return self.minv is not None or self.lut is not None or self.flip_ud or self.flip_lr
+        return self.minv is not None or self.lut is not None or self.flip_ud or self.flip_lr or self.partner is not None
 
     def plain_tensor(self):
         """The underlying tensor when the recipe is exactly one untouched image, else None."""
@@ -289,14 +296,19 @@ class DeviceImage:
         return None
 
     # -- loader worker processes (data/recipe.py): tiles may be LazyImage nodes — shapes without pixels
+    def source_tiles(self):
+        """Every tile the render reads: this recipe's and its MixUp partner's."""
+        return self.tiles if self.partner is None else self.tiles + self.partner.tiles
+
     def has_lazy(self):
-        return any(is_lazy(t[0]) for t in self.tiles)
+        return any(is_lazy(t[0]) for t in self.source_tiles())
 
     def frozen(self):
         """A detached copy of the recipe (what a "render" LazyImage node carries)."""
         c = DeviceImage(list(self.tiles), self.canvas_hw, self.fill)
         c.minv, c.out_hw, c.lut, c.flip_ud, c.flip_lr = self.minv, self.out_hw, self.lut, self.flip_ud, self.flip_lr
         c.was_numpy, c.final_reverse_c = self.was_numpy, self.final_reverse_c
+        c.partner, c.mix_r = (None if self.partner is None else self.partner.frozen()), self.mix_r
         return c
 
     def resolved(self, materialize):
@@ -305,6 +317,8 @@ class DeviceImage:
             return self
         c = self.frozen()
         c.tiles = [(materialize(t[0]), *t[1:]) for t in self.tiles]
+        if c.partner is not None:
+            c.partner = c.partner.resolved(materialize)
         return c
 
     # -- recipe edits
@@ -313,6 +327,7 @@ class DeviceImage:
         h, w = t.shape[:2]
         self.tiles, self.canvas_hw, self.out_hw = [(t, 0, 0, w, h, 0, 0)], (h, w), (h, w)
         self.minv, self.lut, self.flip_ud, self.flip_lr = None, None, False, False
+        self.partner, self.mix_r = None, None
 
     def warp(self, M23, dsize):
         """cv2.warpAffine(img, M23, dsize=(w, h), borderValue=fill) — recorded, not executed."""
@@ -320,6 +335,24 @@ class DeviceImage:
             self._flatten()
         self.minv = invert_affine(M23)
         self.out_hw = (int(dsize[1]), int(dsize[0]))
+        return self
+
+    def mix(self, other, r):
+        """MixUp._mix_transform: (self * r + other * (1 - r)).astype(uint8) — recorded, not executed.  The blend comes after
+        both geometries and before HSV / flips, so a side that already carries colour tables, flips or a partner of its own
+        becomes pixels first; two plain geometry recipes (the pipeline's case) fold into the one launch."""
+        r = float(r)
+        if not 0.0 <= r <= 1.0:
+            raise ValueError(f"DeviceImage.mix: r must be in [0, 1], got {r}")
+        if tuple(other.out_hw) != tuple(self.out_hw):
+            raise ValueError(f"DeviceImage.mix: the images differ in size ({self.out_hw} and {other.out_hw})")
+        if self.lut is not None or self.flip_ud or self.flip_lr or self.partner is not None:
+            self._flatten()
+        other = other.frozen()                                     # the partner's recipe is taken as it is now
+        if other.lut is not None or other.flip_ud or other.flip_lr or other.partner is not None or other.fill != self.fill:
+            other._flatten()
+        self.partner, self.mix_r = other, r
+        self.was_numpy |= other.was_numpy
         return self
 
     def hsv(self, luts):
@@ -346,8 +379,13 @@ class DeviceImage:
             raise RuntimeError("DeviceImage.render: the recipe still holds LazyImage tiles — resolve() it in the training process first")
         if dst is None:
             dst = torch.empty((3, H, W) if chw else (H, W, 3), dtype=dtype, device=self.device)
-        K.image_mosaic_warp(self.tiles, self.canvas_hw, dst, minv=self.minv, hsv_lut=self.lut, flip_ud=self.flip_ud,
-                            flip_lr=self.flip_lr, fill=self.fill, reverse_c=reverse_c, chw=chw)
+        if self.partner is not None:
+            p = self.partner
+            K.image_mixup_warp(self.tiles, self.canvas_hw, self.minv, p.tiles, p.canvas_hw, p.minv, self.mix_r, dst, hsv_lut=self.lut,
+                               flip_ud=self.flip_ud, flip_lr=self.flip_lr, fill=self.fill, reverse_c=reverse_c, chw=chw)
+        else:
+            K.image_mosaic_warp(self.tiles, self.canvas_hw, dst, minv=self.minv, hsv_lut=self.lut, flip_ud=self.flip_ud,
+                                flip_lr=self.flip_lr, fill=self.fill, reverse_c=reverse_c, chw=chw)
         return dst
 
     def unwrap(self):
@@ -384,7 +422,8 @@ def get_rotation_matrix_2d(center, angle, scale):
 # The host side of the training pipeline is a RECIPE GENERATOR: each transform draws its random numbers (in the reference's order,
 # from the reference's two generators — `random` and `np.random` — so that a seeded run consumes the same streams), turns them into
 # geometry (tile rectangles, one 3x3 matrix, three 256-entry tables, two flip bits) recorded on the DeviceImage, and moves the few
-# boxes of the sample through that geometry in float32.  No pixel is touched here; sy11_image_mosaic_warp renders the recipe.
+# boxes of the sample through that geometry in float32.  No pixel is touched here; sy11_image_mosaic_warp (with a MixUp partner:
+# sy11_image_mixup_warp) renders the recipe.
 def mosaic_quadrant(i, xc, yc, w, h, side):
     """Tile ``i`` (bit 0: right column, bit 1: bottom row) of a 2x2 mosaic on a ``side`` x ``side`` canvas whose four tiles meet at
     (xc, yc): the tile's bottom-right / bottom-left / ... corner is pinned to the centre and whatever sticks out of the canvas is
@@ -618,22 +657,40 @@ class RandomFlip:
         return labels
 
 
-class _NoMix:
-    """MixUp(p=0) / the slots of the v8 pipeline this build does not carry: draws what the reference draws, changes nothing."""
+class MixUp:
+    """augment.py:386-407 (BaseMixTransform.__call__), :919 (get_indexes), :944-949 (_mix_transform): one coin (drawn even at
+    p = 0), ONE partner index from the whole dataset, the partner through ``pre_transform`` (in v8_transforms the very Compose the
+    sample went through, so it draws its own mosaic coin, buffer picks, centre and affine parameters), r ~ Beta(32, 32), labels
+    concatenated.  The pixels are not blended here: the partner's geometry and r are recorded on the sample's DeviceImage and the
+    fused render (sy11_image_mixup_warp) blends both in the launch that also does HSV / flips / layout."""
 
-    def __init__(self, p=0.0):
-        if p:
-            raise NotImplementedError("sy11 carries the default detection pipeline (mixup = copy_paste = 0.0)")
+    def __init__(self, dataset, pre_transform=None, p=0.0):
+        self.dataset, self.pre_transform, self.p = dataset, pre_transform, p
+
+    def get_indexes(self):
+        return random.randint(0, len(self.dataset) - 1)
 
     def __call__(self, labels):
-        random.uniform(0, 1)                   # BaseMixTransform.__call__ :386 — the coin is drawn even when p = 0
+        if random.uniform(0, 1) > self.p:                          # draw 1: apply at all?
+            return labels
+        partner = self.dataset.get_image_and_label(self.get_indexes())                      # draw 2
+        if self.pre_transform is not None:
+            partner = self.pre_transform(partner)                  # the partner's own geometry draws
+        return self._mix_transform(labels, partner)
+
+    @staticmethod
+    def _mix_transform(labels, partner):
+        r = np.random.beta(32.0, 32.0)                             # mixup ratio, alpha = beta = 32
+        labels["img"] = DeviceImage.wrap(labels["img"]).mix(DeviceImage.wrap(partner["img"]), r).unwrap()
+        labels["instances"] = Instances.concatenate([labels["instances"], partner["instances"]], axis=0)
+        labels["cls"] = np.concatenate([labels["cls"], partner["cls"]], 0)
         return labels
 
 
 def v8_transforms(dataset, imgsz, hyp, stretch=False):
     """augment.py:2270-2342 for detection defaults: Mosaic -> RandomPerspective (LetterBox pre-transform for the non-mosaic
-    samples) -> [CopyPaste: no segments, no draw] -> MixUp(p=0: one draw) -> [Albumentations: not installed, no draw] ->
-    RandomHSV -> RandomFlip(vertical) -> RandomFlip(horizontal)."""
+    samples) -> [CopyPaste: no segments, no draw] -> MixUp (the partner goes through the same Mosaic -> RandomPerspective object) ->
+    [Albumentations: not installed, no draw] -> RandomHSV -> RandomFlip(vertical) -> RandomFlip(horizontal)."""
     if getattr(hyp, "copy_paste", 0.0):
         raise NotImplementedError("copy_paste needs segment labels (out of scope for detection)")
     geometry = Compose([Mosaic(dataset, imgsz=imgsz, p=hyp.mosaic),
@@ -642,4 +699,4 @@ def v8_transforms(dataset, imgsz, hyp, stretch=False):
                                           pre_transform=None if stretch else LetterBox(new_shape=(imgsz, imgsz)))])
     colour = RandomHSV(hgain=hyp.hsv_h, sgain=hyp.hsv_s, vgain=hyp.hsv_v)
     flips = [RandomFlip(direction=d, p=p) for d, p in (("vertical", hyp.flipud), ("horizontal", hyp.fliplr))]
-    return Compose([geometry, _NoMix(getattr(hyp, "mixup", 0.0)), colour, *flips])
+    return Compose([geometry, MixUp(dataset, pre_transform=geometry, p=getattr(hyp, "mixup", 0.0)), colour, *flips])

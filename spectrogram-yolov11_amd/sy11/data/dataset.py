@@ -514,7 +514,7 @@ class WorkerLoader(InfiniteDataLoader):
                 if node.key() not in self.materialize.cache:
                     self._sources(node.op[1], acc)
             elif node.op[0] == "render":
-                for t in node.op[1].tiles:
+                for t in node.op[1].source_tiles():
                     self._sources(t[0], acc)
 
     def _start_decodes(self, samples):
@@ -522,7 +522,7 @@ class WorkerLoader(InfiniteDataLoader):
         for smp in samples:
             img = smp.get("img")
             if isinstance(img, DeviceImage):
-                for t in img.tiles:
+                for t in img.source_tiles():
                     self._sources(t[0], need)
         ds = self.dataset
         for i in need:

@@ -7,6 +7,8 @@ as ``LazyImage`` nodes: a shape plus how to obtain the pixels later (a source fi
 What crosses the process boundary per sample is ~1.5 KB — tile rectangles, one inverted affine map, three 256-byte colour tables, two
 flip bits, the boxes — and the training process turns it into pixels with one fused launch per sample (sy11_image_mosaic_warp) after
 resolving the source nodes against its cache of decoded images in HBM.
+With MixUp (hyp.mixup > 0) a mixed sample carries a second set of tile rectangles and a second map — its partner's — plus the blend
+weight; both sides resolve the same way and sy11_image_mixup_warp renders them in that one launch.
 """
 from __future__ import annotations
 

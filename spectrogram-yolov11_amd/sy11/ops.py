@@ -484,31 +484,62 @@ def image_letterbox(src, dst, new_hw, top, left, fill=114, reverse_c=False, chw=
     return dst
 
 
+def _pack_tiles(who, tiles, device):
+    """tiles -> (count, host array of device pointers, host array of 8 int32 per tile) as the image_*_warp entries take them."""
+    n = len(tiles)
+    srcs = (C.c_void_p * max(n, 1))()
+    geom = (C.c_int32 * (8 * max(n, 1)))()
+    for t, (src, x1, y1, x2, y2, padw, padh) in enumerate(tiles):
+        if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous() or src.device != device:
+            raise _lib.Sy11Error(f"{who}: every tile must be a contiguous (h, w, 3) uint8 tensor on dst's device")
+        srcs[t] = src.data_ptr()
+        geom[8 * t:8 * t + 8] = [src.shape[0], src.shape[1], int(x1), int(y1), int(x2), int(y2), int(padw), int(padh)]
+    return n, srcs, geom
+
+
+def _pack_lut(who, hsv_lut):
+    """-> (pointer or None, the array that keeps it alive)."""
+    import numpy as np
+    if hsv_lut is None:
+        return None, None
+    lut_np = np.ascontiguousarray(hsv_lut, dtype=np.uint8)
+    if lut_np.size != 768:
+        raise _lib.Sy11Error(f"{who}: hsv_lut must hold 3 x 256 bytes")
+    return lut_np.ctypes.data_as(C.c_void_p), lut_np
+
+
 def image_mosaic_warp(tiles, canvas_hw, dst, minv=None, hsv_lut=None, flip_ud=False, flip_lr=False, fill=114,
                       reverse_c=False, chw=True):
     """Render one augmented sample (sy11_image_mosaic_warp).  tiles = [(src (h, w, 3) uint8 device tensor, x1, y1, x2,
     y2, padw, padh)] (at most 4); minv = 6 floats of the inverted affine map or None; hsv_lut = (3, 256) uint8 numpy
     array or None; dst = (3, H, W) / (H, W, 3) uint8 or float device tensor."""
-    import numpy as np
-    n = len(tiles)
     if dst.dim() != 3 or not dst.is_contiguous() or dst.shape[0 if chw else 2] != 3:
         raise _lib.Sy11Error("image_mosaic_warp: dst must be a contiguous (3, H, W) [chw] or (H, W, 3) tensor")
     H, W = (dst.shape[1], dst.shape[2]) if chw else (dst.shape[0], dst.shape[1])
-    srcs = (C.c_void_p * max(n, 1))()
-    geom = (C.c_int32 * (8 * max(n, 1)))()
-    for t, (src, x1, y1, x2, y2, padw, padh) in enumerate(tiles):
-        if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous() or src.device != dst.device:
-            raise _lib.Sy11Error("image_mosaic_warp: every tile must be a contiguous (h, w, 3) uint8 tensor on dst's device")
-        srcs[t] = src.data_ptr()
-        geom[8 * t:8 * t + 8] = [src.shape[0], src.shape[1], int(x1), int(y1), int(x2), int(y2), int(padw), int(padh)]
+    n, srcs, geom = _pack_tiles("image_mosaic_warp", tiles, dst.device)
     m = (C.c_double * 6)(*[float(v) for v in minv]) if minv is not None else None
-    lut = None
-    if hsv_lut is not None:
-        lut_np = np.ascontiguousarray(hsv_lut, dtype=np.uint8)
-        if lut_np.size != 768:
-            raise _lib.Sy11Error("image_mosaic_warp: hsv_lut must hold 3 x 256 bytes")
-        lut = lut_np.ctypes.data_as(C.c_void_p)
+    lut, _keep = _pack_lut("image_mosaic_warp", hsv_lut)
     call("sy11_image_mosaic_warp", _img_dt(dst), n, srcs, geom, int(canvas_hw[0]), int(canvas_hw[1]), m, H, W, lut,
+         int(bool(flip_ud)), int(bool(flip_lr)), int(fill), int(bool(reverse_c)), int(bool(chw)), _p(dst), _stream())
+    return dst
+
+
+def image_mixup_warp(tiles_a, canvas_hw_a, minv_a, tiles_b, canvas_hw_b, minv_b, r, dst, hsv_lut=None, flip_ud=False,
+                     flip_lr=False, fill=114, reverse_c=False, chw=True):
+    """Render one MixUp sample (sy11_image_mixup_warp): recipe a (the sample) and recipe b (the partner), each as in
+    image_mosaic_warp, blended per pixel as (a * r + b * (1 - r)).astype(uint8) — 1 - r is formed here, in float64 —
+    then hsv_lut / flips / layout as in image_mosaic_warp.  Both recipes must produce dst's H x W."""
+    if dst.dim() != 3 or not dst.is_contiguous() or dst.shape[0 if chw else 2] != 3:
+        raise _lib.Sy11Error("image_mixup_warp: dst must be a contiguous (3, H, W) [chw] or (H, W, 3) tensor")
+    H, W = (dst.shape[1], dst.shape[2]) if chw else (dst.shape[0], dst.shape[1])
+    na, srcs_a, geom_a = _pack_tiles("image_mixup_warp", tiles_a, dst.device)
+    nb, srcs_b, geom_b = _pack_tiles("image_mixup_warp", tiles_b, dst.device)
+    ma = (C.c_double * 6)(*[float(v) for v in minv_a]) if minv_a is not None else None
+    mb = (C.c_double * 6)(*[float(v) for v in minv_b]) if minv_b is not None else None
+    lut, _keep = _pack_lut("image_mixup_warp", hsv_lut)
+    r = float(r)
+    call("sy11_image_mixup_warp", _img_dt(dst), na, srcs_a, geom_a, int(canvas_hw_a[0]), int(canvas_hw_a[1]), ma,
+         nb, srcs_b, geom_b, int(canvas_hw_b[0]), int(canvas_hw_b[1]), mb, r, 1.0 - r, H, W, lut,
          int(bool(flip_ud)), int(bool(flip_lr)), int(fill), int(bool(reverse_c)), int(bool(chw)), _p(dst), _stream())
     return dst
 

@@ -1,6 +1,8 @@
 """Throughput of the image-side kernels at the BASELINE shape (640 x 640, batch 64) and of the whole data path
 (dataset -> fused augmentation -> batch tensor), with the CPU oracle timed beside it.
-  python tools/image_micro.py [--loader]"""
+  python tools/image_micro.py [--loader]
+  python tools/image_micro.py --mixup       only the MixUp comparison: (a) today's sample, (b) the fused MixUp sample, (c) the
+                                            unfused composition (b) replaces, alternated in rounds"""
 import sys
 import tempfile
 import time
@@ -25,7 +27,60 @@ def timeit(fn, reps=20):
     return e0.elapsed_time(e1) / reps
 
 
+def mosaic_tiles(tiles, S, xc, yc):
+    """Four S x S tiles meeting at (xc, yc) on a 2S x 2S canvas, cropped to it."""
+    T = [(tiles[0], xc - S, yc - S, xc, yc, xc - S, yc - S), (tiles[1], xc, yc - S, min(xc + S, 2 * S), yc, xc, yc - S),
+         (tiles[2], xc - S, yc, xc, min(2 * S, yc + S), xc - S, yc), (tiles[3], xc, yc, min(xc + S, 2 * S), min(2 * S, yc + S), xc, yc)]
+    return [(t, max(x1, 0), max(y1, 0), x2, y2, pw, ph) for t, x1, y1, x2, y2, pw, ph in T]
+
+
+def mixup_compare(S=640, rounds=8, reps=50):
+    """(a) one image_mosaic_warp sample, (b) one image_mixup_warp sample (two recipes, one launch), (c) what (b) replaces: two
+    image_mosaic_warp renders into uint8 temporaries + a torch float64 blend + a third image_mosaic_warp for HSV / flips / layout.
+    The variants alternate within every round (rounds x reps launches each), device events around each block of reps."""
+    from sy11.data.augment import invert_affine
+    g = np.random.default_rng(0)
+    src = [torch.from_numpy(g.integers(0, 256, (S, S, 3), dtype=np.uint8)).cuda() for _ in range(8)]
+    Ta, Tb = mosaic_tiles(src[:4], S, 600, 600), mosaic_tiles(src[4:], S, 700, 560)
+    Ma = invert_affine(np.array([[0.9, 0.05, -250.0], [-0.05, 0.9, -260.0]], np.float32))
+    Mb = invert_affine(np.array([[1.1, -0.04, -420.0], [0.06, 1.1, -300.0]], np.float32))
+    lut = np.stack([np.arange(256) % 180, np.clip(np.arange(256) * 1.2, 0, 255), np.clip(np.arange(256) * 0.9, 0, 255)]).astype(np.uint8)
+    r = 0.4718
+    dst = torch.empty((3, S, S), device="cuda")
+    ta, tb = torch.empty((S, S, 3), dtype=torch.uint8, device="cuda"), torch.empty((S, S, 3), dtype=torch.uint8, device="cuda")
+    tail = dict(hsv_lut=lut, flip_ud=True, flip_lr=True, reverse_c=True)
+
+    def a():
+        K.image_mosaic_warp(Ta, (2 * S, 2 * S), dst, minv=Ma, **tail)
+
+    def b():
+        K.image_mixup_warp(Ta, (2 * S, 2 * S), Ma, Tb, (2 * S, 2 * S), Mb, r, dst, **tail)
+
+    def c():
+        K.image_mosaic_warp(Ta, (2 * S, 2 * S), ta, minv=Ma, chw=False)
+        K.image_mosaic_warp(Tb, (2 * S, 2 * S), tb, minv=Mb, chw=False)
+        mixed = (ta.double() * r + tb.double() * (1 - r)).to(torch.uint8)
+        K.image_mosaic_warp([(mixed, 0, 0, S, S, 0, 0)], (S, S), dst, **tail)
+
+    b(); fused = dst.clone(); c()
+    torch.cuda.synchronize()
+    print(f"mixup: fused == unfused composition: {bool(torch.equal(fused, dst))}")
+    t = {"a": [], "b": [], "c": []}
+    for _ in range(rounds):
+        for name, fn in (("a", a), ("b", b), ("c", c)):
+            t[name].append(timeit(fn, reps=reps) * 1e3)
+    for name, what in (("a", "image_mosaic_warp sample (4 tiles, warp+hsv+flips)"), ("b", "image_mixup_warp sample (2 x 4 tiles, fused)"),
+                       ("c", "unfused: 2 x mosaic_warp + torch f64 blend + mosaic_warp")):
+        v = np.array(t[name])
+        print(f"mixup ({name}) {what:58s}: median {np.median(v):6.1f} us  min {v.min():6.1f}  max {v.max():6.1f}  ({rounds} rounds x {reps} launches, incl. host launch)")
+    sa = np.array(t["a"])
+    print(f"mixup: spread of repeated (a) {sa.max() - sa.min():.1f} us; (b)/(a) {np.median(t['b']) / np.median(t['a']):.2f}; "
+          f"(c) - (b) {np.median(t['c']) - np.median(t['b']):.1f} us")
+
+
 def main():
+    if "--mixup" in sys.argv:
+        return mixup_compare()
     B, S = 64, 640
     g = np.random.default_rng(0)
     x8 = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, device="cuda")
