@@ -288,6 +288,19 @@ int sy11_nms_candidates(int32_t B, int32_t D, int32_t A, int32_t nc, float conf_
  * NMS (boxes shifted by class * max_wh never intersect across classes, utils/ops.py:307-312) with n^2 / (2 nc) pair tests.      */
 int sy11_nms_sorted_segments(int32_t nseg, const int32_t* seg_start, const int64_t* seg_ws, int32_t max_n, const float* boxes,
                              float iou_thres, int32_t max_keep, uint64_t* workspace, uint8_t* keep, void* stream);
+/* Seam merge of a long-capture scan (no reference counterpart): the per-window NMS survivors of all W windows — n rows of
+ * {window index, (x1, y1, x2, y2) window-local f32 pixels (16-byte aligned array), score, class}, rows grouped by window in
+ * ascending window order, start[w] (int64 frames, DEVICE array, non-decreasing) the first strip frame of window w — are suppressed
+ * greedily and class-aware (agnostic != 0: across classes) in strip coordinates X = start[w] + x: boxes are visited by (score
+ * descending, row ascending) and a box is dropped when an already-kept one has metric > thres with it (strict), metric 0 = IoU
+ * inter / (a_i + a_j - inter), 1 = IoS inter / min(a_i, a_j).  Pairs are evaluated in f64 relative to one of the two windows, so
+ * starts of 1e9 frames and beyond keep their sub-pixel part.  keep[i] in {0, 1}.  workspace: caller-allocated, 16-byte aligned,
+ * as many bytes as the ..._workspace_bytes query below returns (O(n): no pair matrix).  Synchronises the stream (one host read
+ * per four passes).                                                                                                          */
+int sy11_scan_merge(int32_t n, int32_t W, int32_t n_frames, const int32_t* window, const float* boxes, const float* score,
+                    const int32_t* cls, const int64_t* start, int32_t metric, float thres, int32_t agnostic, void* workspace,
+                    uint8_t* keep, void* stream);
+size_t sy11_scan_merge_workspace_bytes(int32_t n, int32_t W);
 
 /* ---- fused detection criterion (v8DetectionLoss.__call__, utils/loss.py:221-275; TaskAlignedAssigner, utils/tal.py:40-296;
  *      bbox_iou CIoU, utils/metrics.py:171-234).  maps: nl NHWC f32 head maps (B, H_l*W_l, 64+nc); gt: (B, G, 5) rows
@@ -360,6 +373,13 @@ int sy11_stft_minmax_init(int32_t B, float* minmax, void* stream);
 /* img[b,c,f,t] = (db[b,t,f]-min)/(max-min), c = 0..2, NCHW f32 (what preprocess_batch hands the model)        */
 int sy11_stft_normalize(int32_t B, int32_t n_mel, int32_t n_frames, const float* db, const float* minmax,
                         float* img_nchw, void* stream);
+/* Windows from one strip (long-capture scan): db_strip is the (F, n_mel) dB output of sy11_stft_logmel called with B = 1 and
+ * n_frames = F; window w is the n_frames consecutive frames from start[w] (DEVICE array, relative to the strip's first frame,
+ * 0 <= start[w] <= F - n_frames; frames outside the strip read as nothing).  minmax (W, 2): min / max over exactly the window's
+ * n_frames x n_mel rectangle; img (W, 3, n_mel, n_frames) = sy11_stft_normalize's arithmetic per window.  frame_minmax: caller-
+ * allocated scratch of 2 F floats (the per-frame partials: overlapping windows do not re-read the strip).  W <= 65535.        */
+int sy11_stft_windows(int32_t F, int32_t n_mel, int32_t n_frames, int32_t W, const int32_t* start, const float* db_strip,
+                      float* minmax, float* frame_minmax, float* img_nchw, void* stream);
 
 /* ---- image side of preprocess --------------------------------------------------------------
  * batch["img"].float() / 255 of DetectionTrainer.preprocess_batch (models/yolo/detect/train.py:59): n uint8 values

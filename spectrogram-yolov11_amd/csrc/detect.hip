@@ -467,3 +467,133 @@ extern "C" int sy11_box_iou(int32_t n, int32_t m, const float* a, const float* b
   SY11_LAUNCH_CHECK("box_iou");
   return SY11_OK;
 }
+
+// ---- seam merge of a long-capture scan ------------------------------------------------------------------------------------------
+// The per-window NMS survivors of every window of a scan, greedily suppressed across windows in STRIP coordinates (X = start[w] + x):
+// visit boxes by (score descending, row ascending); a box is dropped when an already-kept box of its class (any class: agnostic)
+// has metric > thres with it.  n reaches millions, so there is no n x n mask.  Rows are grouped by window and windows are ordered
+// by start, hence the possible partners of a box (windows whose start is less than n_frames away) are ONE contiguous row range,
+// found once per window.  The greedy result is reached as a fixed point: per pass, one wave per undecided box walks its range and
+// tests the better-ranked partners — KEPT once none of them that is over the threshold is kept or undecided, DROPPED once one is
+// kept.  A decision, once made, is the greedy one (induction over the rank), the best-ranked undecided box is decided in every
+// pass, and a pass reads the states of the previous pass only (two state arrays), so neither the result nor the number of passes
+// depends on scheduling.  Pairs are recomputed per pass instead of stored: memory is O(n).
+// start reaches 1e7 frames and beyond, where f32 loses the sub-pixel part: a pair is evaluated relative to the window of the box
+// being decided (the integer frame delta, |delta| < n_frames, added to the local x) in f64, which makes both exact.
+enum { SCAN_UNDECIDED = 0, SCAN_KEPT = 1, SCAN_DROPPED = 2 };
+
+__global__ __launch_bounds__(256) void scan_row_offsets_kernel(int n, int W, const int* __restrict__ win, int* __restrict__ off) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int cur = min(max(win[i], -1), W - 1);
+  const int prev = i == 0 ? -1 : min(max(win[i - 1], -1), W - 1);
+  for (int w = prev + 1; w <= cur; ++w) off[w] = i;          // first row of every window in (prev, cur]
+  if (i == n - 1) for (int w = cur + 1; w <= W; ++w) off[w] = n;
+}
+
+__global__ __launch_bounds__(256) void scan_row_ranges_kernel(int n, int W, int n_frames, const long long* __restrict__ start,
+                                                              const int* __restrict__ off, int* __restrict__ rlo, int* __restrict__ rhi) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= W) return;
+  const long long s = start[w];
+  int a = w, b = w;
+  while (a > 0 && s - start[a - 1] < n_frames) --a;
+  while (b + 1 < W && start[b + 1] - s < n_frames) ++b;
+  rlo[w] = min(max(off[a], 0), n);
+  rhi[w] = min(max(off[b + 1], 0), n);
+}
+
+__global__ __launch_bounds__(256) void scan_merge_pass_kernel(int n, int W, int n_frames, const int* __restrict__ win, const f32x4* __restrict__ boxes,
+                                                              const float* __restrict__ score, const int* __restrict__ cls,
+                                                              const long long* __restrict__ start, const int* __restrict__ rlo,
+                                                              const int* __restrict__ rhi, int use_ios, double thres, int agnostic,
+                                                              const uint8_t* __restrict__ sin, uint8_t* __restrict__ sout,
+                                                              uint8_t* __restrict__ keep, int* __restrict__ pending) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;                                        // wave-uniform from here on
+  const uint8_t s0 = sin[i];
+  if (s0 != SCAN_UNDECIDED) { if (lane == 0) sout[i] = s0; return; }
+  const int w = win[i];
+  if (w < 0 || w >= W) { if (lane == 0) { sout[i] = SCAN_DROPPED; keep[i] = 0; } return; }
+  const f32x4 bi = boxes[i];
+  const float si = score[i];
+  const int ci = cls[i];
+  const long long sw = start[w];
+  const double ix1 = bi[0], iy1 = bi[1], ix2 = bi[2], iy2 = bi[3];
+  const double ai = (ix2 - ix1) * (iy2 - iy1);
+  bool drop = false, pend = false;
+  const int lo = rlo[w], hi = rhi[w];
+  for (int j = lo + lane; j < hi; j += 64) {
+    if (j == i) continue;
+    const float sj = score[j];
+    if (!(sj > si || (sj == si && j < i))) continue;         // only better-ranked boxes can suppress
+    if (!agnostic && cls[j] != ci) continue;
+    const uint8_t stj = sin[j];
+    if (stj == SCAN_DROPPED) continue;
+    const int wj = win[j];
+    if (wj < 0 || wj >= W) continue;
+    const long long d = start[wj] - sw;
+    if (d <= -(long long)n_frames || d >= (long long)n_frames) continue;
+    const f32x4 bj = boxes[j];
+    const double jx1 = (double)bj[0] + (double)d, jx2 = (double)bj[2] + (double)d, jy1 = bj[1], jy2 = bj[3];
+    const double iw = fmax(0.0, fmin(ix2, jx2) - fmax(ix1, jx1)), ih = fmax(0.0, fmin(iy2, jy2) - fmax(iy1, jy1));
+    const double inter = iw * ih;
+    const double aj = (jx2 - jx1) * (jy2 - jy1);
+    const double metric = use_ios ? inter / fmin(ai, aj) : inter / (ai + aj - inter);
+    if (!(metric > thres)) continue;
+    if (stj == SCAN_KEPT) drop = true; else pend = true;
+  }
+  const bool any_drop = __ballot(drop) != 0, any_pend = __ballot(pend) != 0;
+  if (lane == 0) {
+    if (any_drop) { sout[i] = SCAN_DROPPED; keep[i] = 0; }
+    else if (!any_pend) { sout[i] = SCAN_KEPT; keep[i] = 1; }
+    else { sout[i] = SCAN_UNDECIDED; *pending = 1; }          // same value from every writer
+  }
+}
+
+static inline size_t scan_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+extern "C" size_t sy11_scan_merge_workspace_bytes(int32_t n, int32_t W) {
+  if (n <= 0 || W <= 0) return 0;
+  // row offsets (W + 1), first / last partner row per window (W each), two state arrays (n each), the pending flags of a batch of passes
+  return scan_align16((size_t)(W + 1) * 4) + 2 * scan_align16((size_t)W * 4) + 2 * scan_align16((size_t)n) + 16;
+}
+
+extern "C" int sy11_scan_merge(int32_t n, int32_t W, int32_t n_frames, const int32_t* window, const float* boxes, const float* score,
+                               const int32_t* cls, const int64_t* start, int32_t metric, float thres, int32_t agnostic, void* workspace,
+                               uint8_t* keep, void* stream) {
+  SY11_REQUIRE(n >= 0 && W > 0 && n_frames > 0, "scan_merge: bad dims");
+  SY11_REQUIRE(metric == 0 || metric == 1, "scan_merge: metric must be 0 (iou) or 1 (ios)");
+  if (n == 0) return SY11_OK;
+  SY11_REQUIRE(window && boxes && score && cls && start && workspace && keep, "scan_merge: null pointer");
+  SY11_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "scan_merge: boxes and workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  char* p = (char*)workspace;
+  int* off = (int*)p;        p += scan_align16((size_t)(W + 1) * 4);
+  int* rlo = (int*)p;        p += scan_align16((size_t)W * 4);
+  int* rhi = (int*)p;        p += scan_align16((size_t)W * 4);
+  uint8_t* sa = (uint8_t*)p; p += scan_align16((size_t)n);
+  uint8_t* sb = (uint8_t*)p; p += scan_align16((size_t)n);
+  int* flags = (int*)p;
+  if (hipMemsetAsync(sa, 0, (size_t)n, st) != hipSuccess) SY11_FAIL(SY11_ELAUNCH, "scan_merge: memset failed");
+  hipLaunchKernelGGL(scan_row_offsets_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, W, window, off);
+  SY11_LAUNCH_CHECK("scan_merge (row offsets)");
+  hipLaunchKernelGGL(scan_row_ranges_kernel, dim3(cdiv(W, 256)), dim3(256), 0, st, n, W, n_frames, (const long long*)start, off, rlo, rhi);
+  SY11_LAUNCH_CHECK("scan_merge (row ranges)");
+  // passes in batches of four (an even count: the current states are in `sa` after every batch); one host read per batch.  Every
+  // pass decides at least the best-ranked undecided box, so n passes always suffice.
+  for (long pass = 0; pass < (long)n + 4; pass += 4) {
+    if (hipMemsetAsync(flags, 0, 16, st) != hipSuccess) SY11_FAIL(SY11_ELAUNCH, "scan_merge: memset failed");
+    for (int k = 0; k < 4; ++k) {
+      hipLaunchKernelGGL(scan_merge_pass_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, n, W, n_frames, window, (const f32x4*)boxes, score, cls,
+                         (const long long*)start, rlo, rhi, metric, (double)thres, agnostic, (k & 1) ? sb : sa, (k & 1) ? sa : sb, keep, flags + k);
+      SY11_LAUNCH_CHECK("scan_merge (pass)");
+    }
+    int left = 0;
+    if (hipMemcpyAsync(&left, flags + 3, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      SY11_FAIL(SY11_ELAUNCH, "scan_merge: reading the pending flag failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!left) return SY11_OK;
+  }
+  SY11_FAIL(SY11_ELAUNCH, "scan_merge: no fixed point after n passes");
+}

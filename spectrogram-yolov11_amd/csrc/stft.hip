@@ -433,3 +433,96 @@ extern "C" int sy11_stft_normalize(int32_t B, int32_t n_mel, int32_t n_frames, c
   SY11_LAUNCH_CHECK("stft_normalize");
   return SY11_OK;
 }
+
+// ---- windows from one strip (long-capture scan) -----------------------------------------------------------------------------
+// The strip is the dB spectrogram (F, n_mel) of F consecutive frames (sy11_stft_logmel with B = 1: every frame transformed once,
+// whatever the overlap); window w is the n_frames x n_mel rectangle that starts at frame start[w].  Windows overlap, so the
+// min / max of a window is NOT taken from the strip directly (that would read it W * n_frames / F times): one wave per frame
+// reduces its n_mel values once into frame_minmax (F, 2), and one workgroup per window combines the n_frames partials of its
+// rectangle.  min / max are exact in any order, so the result does not depend on scheduling.  The normalise kernel is
+// stft_normalize_kernel with a per-window base.  A start outside [0, F - n_frames] reads nothing (checked per element).
+__global__ __launch_bounds__(256) void stft_frame_minmax_kernel(int F, int n_mel, const float* __restrict__ db, float* __restrict__ fmm) {
+  const int lane = threadIdx.x & 63;
+  const int frame = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (frame >= F) return;                                    // wave-uniform
+  const float* row = db + (long)frame * n_mel;
+  float mn = INFINITY, mx = -INFINITY;
+  if ((n_mel & 3) == 0 && ((uintptr_t)db & 15) == 0) {
+    const f32x4* row4 = (const f32x4*)row;
+    for (int j = lane; j < (n_mel >> 2); j += 64) {
+      const f32x4 v = row4[j];
+      mn = fminf(fminf(mn, v[0]), fminf(fminf(v[1], v[2]), v[3]));
+      mx = fmaxf(fmaxf(mx, v[0]), fmaxf(fmaxf(v[1], v[2]), v[3]));
+    }
+  } else {
+    for (int j = lane; j < n_mel; j += 64) { const float v = row[j]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+  if (lane == 0) { fmm[2 * frame] = mn; fmm[2 * frame + 1] = mx; }
+}
+
+__global__ __launch_bounds__(256) void stft_window_minmax_kernel(int F, int n_frames, const int* __restrict__ start, const float* __restrict__ fmm,
+                                                                 float* __restrict__ minmax) {
+  __shared__ float rmin[4], rmax[4];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const long s = start[w];
+  float mn = INFINITY, mx = -INFINITY;
+  for (int t = tid; t < n_frames; t += 256) {
+    const long fr = s + t;
+    if (fr >= 0 && fr < F) { mn = fminf(mn, fmm[2 * fr]); mx = fmaxf(mx, fmm[2 * fr + 1]); }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+  if ((tid & 63) == 0) { rmin[tid >> 6] = mn; rmax[tid >> 6] = mx; }
+  __syncthreads();
+  if (tid == 0) {
+    minmax[2 * w] = fminf(fminf(rmin[0], rmin[1]), fminf(rmin[2], rmin[3]));
+    minmax[2 * w + 1] = fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]));
+  }
+}
+
+// img[w][c][f][t] = (db[start[w] + t][f] - min_w) / max(max_w - min_w, 1e-12): the 32x32 LDS transpose of stft_normalize_kernel
+__global__ __launch_bounds__(256) void stft_windows_normalize_kernel(int F, int n_mel, int n_frames, const int* __restrict__ start,
+                                                                     const float* __restrict__ db, const float* __restrict__ minmax,
+                                                                     float* __restrict__ img) {
+  __shared__ float tile[32][33];
+  const int w = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const long s = start[w];
+  const float mn = minmax[2 * w], mx = minmax[2 * w + 1];
+  const float inv = 1.0f / fmaxf(mx - mn, 1e-12f);
+  for (int j = ty; j < 32; j += 8) {
+    const int t = t0 + j, f = f0 + tx;
+    const long fr = s + t;
+    tile[j][tx] = (t < n_frames && f < n_mel && fr >= 0 && fr < F) ? (db[fr * n_mel + f] - mn) * inv : 0.f;
+  }
+  __syncthreads();
+  const long plane = (long)n_mel * n_frames;
+  for (int j = ty; j < 32; j += 8) {
+    const int f = f0 + j, t = t0 + tx;
+    if (f < n_mel && t < n_frames) {
+      const float v = tile[tx][j];
+      float* o = img + (long)w * 3 * plane + (long)f * n_frames + t;
+      o[0] = v; o[plane] = v; o[2 * plane] = v;
+    }
+  }
+}
+
+extern "C" int sy11_stft_windows(int32_t F, int32_t n_mel, int32_t n_frames, int32_t W, const int32_t* start, const float* db_strip,
+                                 float* minmax, float* frame_minmax, float* img_nchw, void* stream) {
+  SY11_REQUIRE(F > 0 && n_mel > 0 && n_frames > 0 && W > 0, "stft_windows: non-positive dims");
+  SY11_REQUIRE(n_frames <= F, "stft_windows: a window of %d frames does not fit in a strip of %d", n_frames, F);
+  SY11_REQUIRE(W <= 65535, "stft_windows: W too large (at most 65535 windows per call)");
+  SY11_REQUIRE((long)F * n_mel < ((long)1 << 40), "stft_windows: strip too large");
+  SY11_REQUIRE(start && db_strip && minmax && frame_minmax && img_nchw, "stft_windows: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(stft_frame_minmax_kernel, dim3(cdiv(F, 4)), dim3(256), 0, st, F, n_mel, db_strip, frame_minmax);
+  SY11_LAUNCH_CHECK("stft_windows (frame min/max)");
+  hipLaunchKernelGGL(stft_window_minmax_kernel, dim3(W), dim3(256), 0, st, F, n_frames, start, frame_minmax, minmax);
+  SY11_LAUNCH_CHECK("stft_windows (window min/max)");
+  hipLaunchKernelGGL(stft_windows_normalize_kernel, dim3(cdiv(n_frames, 32), cdiv(n_mel, 32), W), dim3(256), 0, st, F, n_mel, n_frames, start,
+                     db_strip, minmax, img_nchw);
+  SY11_LAUNCH_CHECK("stft_windows (normalise)");
+  return SY11_OK;
+}

@@ -242,6 +242,22 @@ class YOLO:
 
     __call__ = predict
 
+    def scan(self, source, sample_rate, center_freq=0.0, conf=0.25, iou=0.7, overlap=0.5, batch=64, merge="ios", merge_thres=0.5,
+             max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None):
+        """Detect over a long IQ capture (no reference counterpart) -> ``ScanResults`` with boxes in strip frames / image rows and
+        in seconds / Hz.  ``source``: a 1-D complex64 tensor or ndarray, a ``.npy`` of complex64, or a raw interleaved-float32
+        file (``.cf32`` / ``.fc32`` / ``.iq``), opened with ``np.memmap`` and read chunk by chunk.  ``sample_rate`` in Hz,
+        ``center_freq`` the RF centre the capture was tuned to.  See ``DetectionPredictor.scan`` for ``overlap`` / ``merge``."""
+        from ..data.spectrogram import SpectrogramProducer, open_iq
+        from .predictor import DetectionPredictor
+        key = (conf, iou, max_det, classes if classes is None else tuple(classes), agnostic_nms, half)
+        if getattr(self, "_scanner_key", None) != key:
+            self._scanner = DetectionPredictor(self.model, device=self.device, conf=conf, iou=iou, max_det=max_det, classes=classes,
+                                               agnostic_nms=agnostic_nms, half=half, producer=SpectrogramProducer(self.device))
+            self._scanner_key = key
+        return self._scanner.scan(open_iq(source), sample_rate, center_freq=center_freq, overlap=overlap, batch=batch, merge=merge,
+                                  merge_thres=merge_thres, stride_frames=stride_frames)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import threading
 
+import numpy as np
 import torch
 
 from ..utils import ops
@@ -51,6 +52,20 @@ class Results:
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
+
+
+class ScanResults:
+    """Detections of a long-capture scan (``DetectionPredictor.scan``), one row per box:
+    ``boxes`` (n, 6) float64 [X1, y1, X2, y2, conf, cls] — X in strip frames (window start + window-local x), y in image rows;
+    ``window`` (n,) int64 the window a box was found in; ``tf`` (n, 4) float64 [t0_s, f_lo_hz, t1_s, f_hi_hz];
+    ``start`` (W,) int64 first frame of every window."""
+
+    def __init__(self, boxes, window, tf, names, start, sample_rate, center_freq):
+        self.boxes, self.window, self.tf, self.names = boxes, window, tf, names
+        self.start, self.sample_rate, self.center_freq = start, sample_rate, center_freq
+
+    def __len__(self):
+        return self.boxes.shape[0]
 
 
 class DetectionPredictor:
@@ -126,3 +141,65 @@ class DetectionPredictor:
             im = self.preprocess(source)
             preds = self.inference(im)
             return self.postprocess(preds, im, orig_imgs, paths)
+
+    @torch.no_grad()
+    def scan(self, iq, sample_rate, center_freq=0.0, overlap=0.5, batch=64, merge="ios", merge_thres=0.5, stride_frames=None,
+             start=None):
+        """Run the model over a capture of any length -> ``ScanResults``.  ``iq``: what ``sy11.data.spectrogram.open_iq`` returns
+        (1-D complex64 samples: array, tensor or ``np.memmap``).  Windows come from ``plan_windows(len(iq), overlap | stride_frames)``
+        (or ``start``); per chunk of ``batch`` windows: the producer's strip images -> ``inference`` (graph replay for full chunks,
+        a second signature for the ragged last one) -> ``non_max_suppression`` with this predictor's conf / iou / max_det.  After
+        the last chunk ONE seam merge (``ops.scan_merge``) suppresses, in strip coordinates, the boxes that overlapping windows
+        found twice: ``merge`` = "ios" (intersection over the smaller area: a box cut by a window edge matches its full twin from
+        the neighbouring window, which IoU does not), "iou", or None for the unmerged rows.  ``merge_thres`` = 0.5 for "ios" is a
+        default chosen by judgement, not a measured optimum."""
+        from .. import ops as kops
+        from ..data import spectrogram as sp
+        if self.producer is None:
+            raise ValueError("scan needs a SpectrogramProducer")
+        if merge not in (None, "ios", "iou"):
+            raise ValueError(f"merge must be 'ios', 'iou' or None, got {merge!r}")
+        p = self.producer
+        if (p.n_mel, p.n_frames) != tuple(self.imgsz):
+            raise ValueError(f"the producer's {p.n_mel} x {p.n_frames} images do not match imgsz={self.imgsz}")
+        if start is None:
+            start = sp.plan_windows(len(iq), overlap, stride_frames, p.n_fft, p.hop, p.n_frames)
+        start = np.asarray(start, dtype=np.int64).reshape(-1)
+        a = self.args
+        rows, wins = [], []
+        with self._lock:
+            buf = torch.empty((min(batch, max(start.size, 1)), 3, p.n_mel, p.n_frames), dtype=torch.float32, device=self.device)
+            w0 = 0
+            for img, st in p.scan(iq, start, chunk_windows=batch, out=buf):
+                preds = ops.non_max_suppression(self.inference(img), a["conf"], a["iou"], classes=a["classes"], agnostic=a["agnostic_nms"],
+                                                max_det=a["max_det"])
+                for k, pr in enumerate(preds):
+                    pr = pr[:, :6].float().clone()
+                    ops.clip_boxes(pr[:, :4], img.shape[2:])                 # what postprocess's scale_boxes comes to at gain 1
+                    rows.append(pr)
+                    wins.append(torch.full((pr.shape[0],), w0 + k, dtype=torch.int32, device=pr.device))
+                w0 += len(st)
+            rows = torch.cat(rows) if rows else torch.zeros((0, 6), dtype=torch.float32, device=self.device)
+            wins = torch.cat(wins) if wins else torch.zeros((0,), dtype=torch.int32, device=self.device)
+            if merge is not None and rows.shape[0]:
+                keep = kops.scan_merge(wins, rows[:, :4].contiguous(), rows[:, 4].contiguous(), rows[:, 5].to(torch.int32), start, p.n_frames,
+                                       metric=merge, thres=merge_thres, agnostic=a["agnostic_nms"])
+                rows, wins = rows[keep], wins[keep]
+        rows, wins = rows.cpu(), wins.cpu().to(torch.int64)
+        boxes = rows.to(torch.float64)
+        off = torch.from_numpy(start)[wins].to(torch.float64)
+        boxes[:, 0] += off
+        boxes[:, 2] += off
+        tf = scan_boxes_to_tf(boxes, sample_rate, center_freq, p)
+        return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq))
+
+
+def scan_boxes_to_tf(boxes, sample_rate, center_freq, producer):
+    """(n, >= 4) float64 [X1, y1, X2, y2] in strip frames / image rows -> (n, 4) float64 [t0_s, f_lo_hz, t1_s, f_hi_hz]; a pixel
+    edge at coordinate c is row / column c - 0.5.  Rows grow with frequency, so y1 is the low edge."""
+    from ..data.spectrogram import cols_to_time, rows_to_freq
+    b = boxes[:, :4].to(torch.float64).numpy()
+    alpha = getattr(producer, "warp_alpha", 1.25)
+    t0, t1 = (cols_to_time(b[:, i] - 0.5, sample_rate, producer.n_fft, producer.hop) for i in (0, 2))
+    f0, f1 = (rows_to_freq(b[:, i] - 0.5, sample_rate, center_freq, producer.n_fft, producer.n_mel, alpha) for i in (1, 3))
+    return torch.from_numpy(np.stack((t0, f0, t1, f1), 1))

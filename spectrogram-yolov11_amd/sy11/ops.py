@@ -440,6 +440,58 @@ def stft_normalize(db, mm, out=None):
     return img
 
 
+def stft_windows(db_strip, start, n_frames, out=None):
+    """Windows of ``n_frames`` frames cut from one dB strip: ``db_strip`` (F, n_mel) f32 (``stft_logmel(...)[0][0]`` of one
+    run of consecutive frames), ``start`` (W,) int32 on the device, relative to the strip's first frame ->
+    (img (W, 3, n_mel, n_frames) f32 in [0, 1], minmax (W, 2) over exactly each window's rectangle)."""
+    _need_gpu(db_strip, start)
+    if db_strip.dim() != 2 or db_strip.dtype != torch.float32 or not db_strip.is_contiguous():
+        raise _lib.Sy11Error("stft_windows: the strip must be a contiguous f32 (F, n_mel) tensor")
+    if start.dtype != torch.int32 or start.dim() != 1 or not start.is_contiguous() or start.numel() == 0:
+        raise _lib.Sy11Error("stft_windows: `start` must be a non-empty contiguous int32 vector")
+    F, n_mel = db_strip.shape
+    W = start.numel()
+    if out is not None and (tuple(out.shape) != (W, 3, n_mel, n_frames) or out.dtype != torch.float32 or not out.is_contiguous()
+                            or out.device != db_strip.device):
+        raise _lib.Sy11Error("stft_windows: `out` must be a contiguous f32 (W, 3, n_mel, n_frames) tensor on the same device")
+    img = out if out is not None else torch.empty((W, 3, n_mel, n_frames), dtype=torch.float32, device=db_strip.device)
+    mm = torch.empty((W, 2), dtype=torch.float32, device=db_strip.device)
+    fmm = torch.empty((F, 2), dtype=torch.float32, device=db_strip.device)
+    call("sy11_stft_windows", F, n_mel, int(n_frames), W, _p(start), _p(db_strip), _p(mm), _p(fmm), _p(img), _stream())
+    return img, mm
+
+
+SCAN_METRICS = {"iou": 0, "ios": 1}
+
+
+def scan_merge(window, boxes, score, cls, start, n_frames, metric="ios", thres=0.5, agnostic=False):
+    """Seam merge of a scan's per-window survivors: ``window`` (n,) int32 (non-decreasing), ``boxes`` (n, 4) f32 window-local xyxy,
+    ``score`` (n,) f32, ``cls`` (n,) int32, ``start`` (W,) int64 first strip frame of every window (non-decreasing; host or device)
+    -> bool keep mask (n,): greedy class-aware suppression in strip coordinates (include/sy11.h)."""
+    _need_gpu(window, boxes, score, cls)
+    if metric not in SCAN_METRICS:
+        raise _lib.Sy11Error(f"scan_merge: metric must be one of {sorted(SCAN_METRICS)}, got {metric!r}")
+    n = window.shape[0]
+    dev = boxes.device
+    start = torch.as_tensor(start, dtype=torch.int64)
+    W = start.numel()
+    if boxes.shape != (n, 4) or score.shape != (n,) or cls.shape != (n,) or W == 0:
+        raise _lib.Sy11Error("scan_merge: expected window (n,), boxes (n, 4), score (n,), cls (n,) and a non-empty start")
+    if W > 1 and bool((start[1:] < start[:-1]).any()):
+        raise _lib.Sy11Error("scan_merge: `start` must be non-decreasing")
+    keep = torch.zeros((n,), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return keep.bool()
+    window = window.to(torch.int32).contiguous()
+    if bool((window[1:] < window[:-1]).any()) or int(window[0]) < 0 or int(window[-1]) >= W:
+        raise _lib.Sy11Error("scan_merge: rows must be grouped by window, in ascending window order, with 0 <= window < len(start)")
+    ws = torch.empty((_lib.load().sy11_scan_merge_workspace_bytes(n, W),), dtype=torch.uint8, device=dev)
+    call("sy11_scan_merge", n, W, int(n_frames), _p(window), _p(boxes.float().contiguous()), _p(score.float().contiguous()),
+         _p(cls.to(torch.int32).contiguous()), _p(start.to(dev).contiguous()), SCAN_METRICS[metric], float(thres), 1 if agnostic else 0,
+         _p(ws), _p(keep), _stream())
+    return keep.bool()
+
+
 # ------------------------------------------------------------------------------------------------ image side of preprocess
 def _img_dt(t):
     return _lib.U8 if t.dtype == torch.uint8 else _DT[t.dtype]
