@@ -88,7 +88,9 @@ __global__ __launch_bounds__(256) void loss_decode_kernel(const LossArgs a) {
   anchor_of(a, an, l, gx, gy);
   const float* row = a.maps[l] + ((long)b * a.hs[l] * a.ws[l] + (an - a.a0[l])) * a.no + sd * REG;
   float x[16];
-  if ((a.no & 3) == 0) {                                       // rows of 64 + nc floats start 16-byte aligned when nc % 4 == 0
+  // rows of 64 + nc floats are 16-byte aligned when nc % 4 == 0 AND the map itself is (a view may start anywhere in its allocation):
+  // the same test as loss_terms_kernel's; either branch fills x[] with the same values
+  if ((a.no & 3) == 0 && ((uintptr_t)row & 15) == 0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const f32x4 v = *(const f32x4*)(row + 4 * i);
@@ -423,11 +425,16 @@ extern "C" int sy11_det_loss_assign(int32_t B, int32_t nc, int32_t nl, const flo
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const long BA = (long)B * a.A;
+  const size_t lds = (size_t)a.A * 4;
+  if (G > 0) {                                      // every refusal comes before the first launch
+    SY11_REQUIRE(gt && align && overlap && topk && pos, "det_loss: null workspace");
+    // with fewer anchors than TOPK a selection round finds no candidate and thread 0 would mark s_al[0x7fffffff]
+    // (the reference's torch.topk refuses k > A as well)
+    SY11_REQUIRE(a.A >= TOPK, "det_loss: %d anchors are fewer than the top-%d of the assignment", a.A, TOPK);
+    SY11_REQUIRE(lds <= 150 * 1024, "det_loss: %d anchors exceed the LDS top-k buffer", a.A);
+  }
   hipLaunchKernelGGL(loss_decode_kernel, dim3((unsigned)((BA * 4 + 255) / 256)), dim3(256), 0, st, a);
   if (G > 0) {
-    SY11_REQUIRE(gt && align && overlap && topk && pos, "det_loss: null workspace");
-    const size_t lds = (size_t)a.A * 4;
-    SY11_REQUIRE(lds <= 150 * 1024, "det_loss: %d anchors exceed the LDS top-k buffer", a.A);
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)loss_tal_metrics_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(loss_tal_metrics_kernel, dim3(G, B), dim3(256), lds, st, a);
   }

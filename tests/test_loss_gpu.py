@@ -36,20 +36,51 @@ def make_case(B, nc, hw, n_gt, seed):
     return maps, batch
 
 
+def make_large_case(nc, hw, seed):
+    """One box over nearly the whole 128-pixel image per image, and head maps shaped so that the assigner's positives land on another
+    level in each image: image 0 keeps the random maps (stride 8 wins) and its stride-8 anchor (15, 8) predicts its target well and
+    scores high, so it is among the ten although its left distance (124 - 1.92) / 8 = 15.26 bins is past the DFL clamp; in image 1
+    (image 2) the distributions of the other levels lean to bin 0 and those of stride 16 (stride 32) to the target's half width."""
+    B = 3
+    g = torch.Generator().manual_seed(seed)
+    maps = [torch.randn(B, 64 + nc, h, w, generator=g) * 1.5 for h, w in hw]
+    j = torch.arange(16.0).repeat(4).view(1, 64, 1, 1)
+    for b, good, centre in ((1, 1, 4.0), (2, 2, 2.0)):
+        for l in range(3):
+            maps[l][b:b + 1, :64] += -0.3 * (j - centre) ** 2 if l == good else -1.0 * j
+    m = maps[0][0]
+    m[:64, 8, 15] = -4.0
+    for s, k in enumerate((15, 8, 0, 7)):
+        m[s * 16 + k, 8, 15] = 8.0
+    m[64:, 8, 15] = 6.0
+    bb = [[0.5, 0.5, 0.97 - 0.01 * b, 0.96 + 0.01 * b] for b in range(B)]
+    batch = {"batch_idx": torch.arange(B).float(), "cls": torch.tensor([[1.0], [0.0], [float(nc - 1)]]), "bboxes": torch.tensor(bb)}
+    return maps, batch
+
+
 @pytest.mark.parametrize("B,nc,hw,n_gt,seed", [
     (2, 80, [(16, 16), (8, 8), (4, 4)], [3, 1], 0),
     (3, 5, [(20, 12), (10, 6), (5, 3)], [4, 0, 2], 1),          # an image without targets, non-square maps
     (2, 2, [(8, 8), (4, 4), (2, 2)], [6], 2),                   # many overlapping boxes -> multi-gt conflicts
     (2, 80, [(8, 8), (4, 4), (2, 2)], [0], 3),                  # a batch without a single target (utils/loss.py:197-198): background BCE only
     (1, 3, [(4, 4), (2, 2), (1, 1)], [2], 4),                   # one image, 21 anchors: fewer candidates per level than topk = 10 at the coarse levels
+    (3, 4, [(16, 16), (8, 8), (4, 4)], "large", 5),             # positives on strides 16 and 32, a stride-8 target distance past the DFL clamp
 ])
 def test_fused_loss_matches_oracle(B, nc, hw, n_gt, seed):
     from sy11 import ops as K
-    maps, batch = make_case(B, nc, hw, n_gt, seed)
+    maps, batch = make_large_case(nc, hw, seed) if n_gt == "large" else make_case(B, nc, hw, n_gt, seed)
     # oracle (CPU, autograd)
     om = [m.clone().requires_grad_(True) for m in maps]
     oloss, oitems, (t_labels, t_boxes, t_scores, fg, gt_idx) = loss_ref.detection_loss(om, batch, nc=nc, return_targets=True)
     oloss.backward()
+    if n_gt == "large":
+        a1, a2 = hw[0][0] * hw[0][1], hw[0][0] * hw[0][1] + hw[1][0] * hw[1][1]
+        weighted = fg.bool() & (t_scores.sum(-1) > 0)
+        assert weighted[:, a1:a2].sum() >= 8 and weighted[:, a2:].sum() >= 8, "no positives on strides 16 / 32"
+        xs, ys = (torch.arange(16) + 0.5).repeat(16), (torch.arange(16) + 0.5).repeat_interleave(16)
+        t = t_boxes[:, :a1] / 8
+        dist = torch.stack((xs - t[..., 0], ys - t[..., 1], t[..., 2] - xs, t[..., 3] - ys), -1)
+        assert dist[weighted[:, :a1]].max() > 14.99, "no stride-8 target distance past the DFL clamp"
     # device
     c = crit(nc)
     feats = [m.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_(True) for m in maps]
