@@ -431,6 +431,32 @@ int sy11_image_mixup_warp(int32_t dtype, int32_t n_tiles_a, const uint8_t* const
                           const uint8_t* hsv_lut, int32_t flip_ud, int32_t flip_lr, int32_t fill,
                           int32_t reverse_c, int32_t chw, void* dst, void* stream);
 
+/* ---- IQ side of the training loader (no reference code: the reference trains from rendered images; spec in DESIGN.md §4) ----
+ * One launch gathers a window of L samples per batch row out of captures resident in device memory and applies the IQ-domain
+ * augmentation recipe of that row:
+ *   out[b n] = gain rot(c(src[off + n])  phi0 + n dphi) + gain2 rot(c2(src2[off2 + n])  phi02 + n dphi2) + sigma w(seed  n)
+ * src = (const complex64*) src_ptr[b], off = src_off[b] in SAMPLES (may be odd); c / c2 = optional conjugate (flags).
+ * dphi / phi0: uint32 fractions of a cycle; phi0 + n dphi is taken in wrapping uint32 arithmetic (exact for every n) and becomes
+ * an angle in [-pi pi) for one sincos.  w: unit-variance complex normal from Philox4x32-10 with key = seed and counter
+ * (n / 2  0  0  0): words 0 1 give sample 2k, words 2 3 sample 2k + 1, each by Box-Muller on (x + 0.5) 2^-32 (radius sqrt(-ln u1),
+ * angle 2 pi u2), so a sample depends on (seed n) only.  src2 = 0: no partner.  Steps that are off are skipped: gain 1, dphi =
+ * phi0 = 0, no conjugate, no partner, sigma 0 copies the source bit for bit.
+ * src_ptr / src_off / r are DEVICE arrays of B entries; out (B L) interleaved complex64.  The caller guarantees that
+ * [off  off + L) and [off2  off2 + L) lie inside their captures.  B <= 65535 and B * L < 2^31.                          */
+enum { SY11_IQ_CONJ = 1, SY11_IQ_CONJ2 = 2 };
+typedef struct sy11_iq_recipe {
+  uint32_t dphi, phi0;         /* phase step per sample and phase of sample 0, in 2^-32 cycles                    */
+  float gain, sigma;           /* linear gain of the sample's own window; noise standard deviation (complex)      */
+  uint64_t seed;               /* Philox key                                                                      */
+  uint64_t src2;               /* partner capture (device address of complex64 samples) or 0                      */
+  int64_t off2;                /* partner's first sample                                                          */
+  uint32_t dphi2, phi02;
+  float gain2;
+  uint32_t flags;              /* SY11_IQ_CONJ | SY11_IQ_CONJ2                                                    */
+} sy11_iq_recipe;
+int sy11_iq_gather_augment(int32_t B, int32_t L, const uint64_t* src_ptr, const int64_t* src_off, const sy11_iq_recipe* r,
+                           float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,15 @@ class OptDesc(C.Structure):
                 ("growth_interval", C.c_int32), ("nparts", C.c_int32)]
 
 
+class IqRecipe(C.Structure):
+    """sy11_iq_recipe: one batch row of sy11_iq_gather_augment (include/sy11.h)."""
+    _fields_ = [("dphi", C.c_uint32), ("phi0", C.c_uint32), ("gain", C.c_float), ("sigma", C.c_float), ("seed", C.c_uint64),
+                ("src2", C.c_uint64), ("off2", C.c_int64), ("dphi2", C.c_uint32), ("phi02", C.c_uint32), ("gain2", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+IQ_CONJ, IQ_CONJ2 = 1, 2
+
 _vp, _i32, _i64, _f32, _f64, _u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32
 _dp = C.POINTER(ConvDesc)
 _bp = C.POINTER(BnTail)
@@ -103,6 +112,7 @@ SIGNATURES = {
     "sy11_image_mosaic_warp": [_i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "sy11_image_mixup_warp": [_i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _f64, _f64, _i32, _i32, _vp, _i32, _i32,
                               _i32, _i32, _i32, _vp, _vp],
+    "sy11_iq_gather_augment": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],

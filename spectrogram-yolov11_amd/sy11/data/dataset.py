@@ -618,7 +618,12 @@ def build_dataloader(dataset, batch, workers=8, shuffle=True, rank=-1, world_siz
     """data/build.py:129-157.  ``workers``: as in the reference, the loader's parallelism.  Training datasets (augment, no rect) get
     min(workers, CPUs - 1, 8) recipe WORKER PROCESSES (``WorkerLoader``) plus as many decode threads; validation / rect datasets and
     workers <= 1 stay in-process (``InfiniteDataLoader``: decode threads only).  ``procs`` (or SY11_LOADER_PROCS) overrides the count,
-    0 = in-process."""
+    0 = in-process.  An ``IQDataset`` always keeps its recipes in the training process, whatever ``workers`` says (``workers=0``
+    semantics, ``IQDataLoader``): drawing a recipe costs a few microseconds per sample and the samples never leave the device, so
+    there is nothing for a worker process to take over."""
+    from .iq_dataset import IQDataLoader, IQDataset
+    if isinstance(dataset, IQDataset):
+        return IQDataLoader(dataset, batch, shuffle=shuffle, rank=rank, world_size=world_size)
     ncpu = os.cpu_count() or 1
     threads = max(min(workers, ncpu), 0)
     if procs is None:

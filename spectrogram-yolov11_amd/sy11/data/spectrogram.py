@@ -115,6 +115,21 @@ def cols_to_time(X, sample_rate, n_fft=1024, hop=256):
     return (np.asarray(X, dtype=np.float64) * hop + n_fft / 2) / float(sample_rate)
 
 
+def freq_to_rows(hz, sample_rate, center_freq=0.0, n_fft=1024, n_mel=640, warp_alpha=1.25):
+    """Hz -> image row (float64), the inverse of ``rows_to_freq``: a frequency that is the low / high edge of a box sits at pixel
+    coordinate ``row + 0.5``.  Frequencies outside the band map outside [-1, n_mel] (the warp is continued, nothing is clipped)."""
+    b = ((np.asarray(hz, dtype=np.float64) - float(center_freq)) / float(sample_rate) + 0.5) * n_fft
+    u = b / ((n_fft / 2) * (n_fft - 1) / n_fft) - 1.0
+    m = np.sign(u) * np.log1p(np.abs(u) * warp_alpha) / math.log1p(warp_alpha)
+    return (m + 1.0) * (n_mel + 1) / 2.0 - 1.0
+
+
+def time_to_cols(t, sample_rate, n_fft=1024, hop=256):
+    """Seconds from the first sample of the capture -> strip column (float64), the inverse of ``cols_to_time``; a box edge at that
+    time sits at pixel coordinate ``col + 0.5``."""
+    return (np.asarray(t, dtype=np.float64) * float(sample_rate) - n_fft / 2) / hop
+
+
 class SpectrogramProducer:
     def __init__(self, device="cuda", n_fft=1024, hop=256, n_frames=640, n_mel=640, warp_alpha=1.25, mel_taps=8):
         self.n_fft, self.hop, self.n_frames, self.n_mel, self.mel_taps = n_fft, hop, n_frames, n_mel, mel_taps

@@ -57,7 +57,30 @@ def check_det_dataset(data):
         if data.get(k):
             x = data[k]
             data[k] = str((root / x).resolve()) if isinstance(x, str) else [str((root / v).resolve()) for v in x]
+    if "kind" in data:                                       # `kind: iq` — labelled IQ captures (sy11/data/iq_dataset.py); no key: images
+        if data["kind"] != "iq":
+            raise SyntaxError(f"'kind: {data['kind']}' is not a dataset kind (only 'iq'; leave the key out for images)")
+        if "sample_rate" not in data:
+            raise SyntaxError("'sample_rate:' (Hz) is required in a 'kind: iq' data YAML")
+        data["sample_rate"], data["center_freq"] = float(data["sample_rate"]), float(data.get("center_freq", 0.0))
+        data["n_fft"], data["hop"] = int(data.get("n_fft", 1024)), int(data.get("hop", 256))
+        if not (data["sample_rate"] > 0 and np.isfinite(data["center_freq"])) or data["n_fft"] < 2 or data["hop"] < 1:
+            raise SyntaxError("'sample_rate' must be positive, 'center_freq' finite, 'n_fft' >= 2 and 'hop' >= 1")
     return data
+
+
+def _iq_setup(data, imgsz, overrides, dev):
+    """What a `kind: iq` run needs besides the dataset: the producer that turns batch["iq"] into images, after refusing the settings
+    that belong to the image path (every image augmentation counts as off for IQ; naming one with a value that would switch it on
+    is an error, as `perspective` is for the image transforms)."""
+    from ..data.dataset import DEFAULT_HYP
+    from ..data.spectrogram import SpectrogramProducer
+    bad = sorted(k for k in overrides if (k in DEFAULT_HYP or k in ("rect", "multi_scale")) and overrides[k] and k not in ("mask_ratio", "overlap_mask"))
+    if bad:
+        raise ValueError(f"{bad} do(es) not apply to a 'kind: iq' dataset (IQ augmentation is iq_shift / iq_conj / iq_gain_db / iq_noise_db / iq_mixup)")
+    if not isinstance(imgsz, int):
+        raise ValueError("a 'kind: iq' dataset needs a square integer imgsz (n_frames = n_mel = imgsz)")
+    return SpectrogramProducer(dev, data["n_fft"], data["hop"], imgsz, imgsz)
 
 
 class YOLO:
@@ -140,19 +163,29 @@ class YOLO:
         model = self._nc_model(data["nc"], data["names"])
         tr_over = {k: v for k, v in overrides.items() if k in _TRAIN_KEYS}
         tr_over["imgsz"] = imgsz
-        self.trainer = DetectionTrainer(model, batch_size=batch, device=dev, overrides=tr_over, world_size=world)
+        iq = data.get("kind") == "iq"
+        producer = _iq_setup(data, imgsz, overrides, dev) if iq else None
+        self.trainer = DetectionTrainer(model, batch_size=batch, device=dev, overrides=tr_over, world_size=world, producer=producer)
+        if iq:                                                                   # recorded in the checkpoint's train_args: `scan` needs
+            for k in ("sample_rate", "center_freq", "n_fft", "hop"):             # the same transform the model was trained on
+                setattr(self.trainer.args, k, data[k])
         if resume and self.ckpt is not None:
             start = self.trainer.resume_training(self.ckpt)
         else:
             start = 0
         hyp = SimpleNamespace(**{**_hyp_defaults(), **{k: v for k, v in overrides.items() if k in _hyp_defaults()}}, imgsz=imgsz)
         stride = int(max(model.stride))
-        ds = build_yolo_dataset(hyp, data["train"], batch, data, mode="train", stride=stride, device=dev)
+        if iq:
+            from ..data.iq_dataset import build_iq_dataset
+            ds = build_iq_dataset(hyp, data["train"], batch, data, mode="train", device=dev)
+        else:
+            ds = build_yolo_dataset(hyp, data["train"], batch, data, mode="train", stride=stride, device=dev)
         dl = build_dataloader(ds, batch, workers=workers, shuffle=True, rank=rank if world > 1 else -1, world_size=world,
                               out=self.trainer.batch_buffer(imgsz), dtype=torch.float32)
         val_batches = None
         if val and data.get("val"):
-            vds = build_yolo_dataset(hyp, data["val"], batch * 2, data, mode="val", rect=True, stride=stride, device=dev)
+            vds = (build_iq_dataset(hyp, data["val"], batch * 2, data, mode="val", device=dev) if iq else
+                   build_yolo_dataset(hyp, data["val"], batch * 2, data, mode="val", rect=True, stride=stride, device=dev))
             vdl = build_dataloader(vds, batch * 2, workers=workers, shuffle=False)
             val_batches = lambda: vdl                                                                            # noqa: E731
         save_dir = save_dir or Path("runs") / "detect" / "train"
@@ -217,9 +250,15 @@ class YOLO:
         data = check_det_dataset(data)
         hyp = SimpleNamespace(**_hyp_defaults(), imgsz=imgsz)
         self.model.names = data["names"]
-        vds = build_yolo_dataset(hyp, data["val"], batch, data, mode="val", rect=True, stride=int(max(self.model.stride)), device=self.device)
+        producer = None
+        if data.get("kind") == "iq":
+            from ..data.iq_dataset import build_iq_dataset
+            producer = _iq_setup(data, imgsz, {}, self.device)
+            vds = build_iq_dataset(hyp, data["val"], batch, data, mode="val", device=self.device)
+        else:
+            vds = build_yolo_dataset(hyp, data["val"], batch, data, mode="val", rect=True, stride=int(max(self.model.stride)), device=self.device)
         vdl = build_dataloader(vds, batch, workers=workers, shuffle=False)
-        self.metrics = DetectionValidator(self.model, device=self.device, conf=conf, iou=iou, half=half)(self.model, vdl)
+        self.metrics = DetectionValidator(self.model, device=self.device, conf=conf, iou=iou, half=half, producer=producer)(self.model, vdl)
         return self.metrics
 
     def predict(self, source, conf=0.25, iou=0.7, imgsz=640, max_det=300, classes=None, agnostic_nms=False, half=False, **kw):
@@ -243,17 +282,25 @@ class YOLO:
     __call__ = predict
 
     def scan(self, source, sample_rate, center_freq=0.0, conf=0.25, iou=0.7, overlap=0.5, batch=64, merge="ios", merge_thres=0.5,
-             max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None):
+             max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None, n_fft=1024, hop=256, imgsz=640):
         """Detect over a long IQ capture (no reference counterpart) -> ``ScanResults`` with boxes in strip frames / image rows and
         in seconds / Hz.  ``source``: a 1-D complex64 tensor or ndarray, a ``.npy`` of complex64, or a raw interleaved-float32
         file (``.cf32`` / ``.fc32`` / ``.iq``), opened with ``np.memmap`` and read chunk by chunk.  ``sample_rate`` in Hz,
-        ``center_freq`` the RF centre the capture was tuned to.  See ``DetectionPredictor.scan`` for ``overlap`` / ``merge``."""
+        ``center_freq`` the RF centre the capture was tuned to.  See ``DetectionPredictor.scan`` for ``overlap`` / ``merge``.
+        ``n_fft`` / ``hop`` / ``imgsz`` (n_frames = n_mel) select the transform; a model trained from IQ captures records its own in
+        the checkpoint, and a scan with another one warns (its results are those of the transform asked for)."""
         from ..data.spectrogram import SpectrogramProducer, open_iq
         from .predictor import DetectionPredictor
-        key = (conf, iou, max_det, classes if classes is None else tuple(classes), agnostic_nms, half)
+        trained = (self.ckpt or {}).get("train_args") or {}
+        if "n_fft" in trained and (trained["n_fft"], trained["hop"], trained.get("imgsz", imgsz)) != (n_fft, hop, imgsz):
+            import warnings                                   # the results are those of the transform asked for, as they always were
+            warnings.warn(f"scan(n_fft={n_fft}, hop={hop}, imgsz={imgsz}) differs from the transform this model was trained on "
+                          f"(n_fft={trained['n_fft']}, hop={trained['hop']}, imgsz={trained.get('imgsz')})", stacklevel=2)
+        key = (conf, iou, max_det, classes if classes is None else tuple(classes), agnostic_nms, half, n_fft, hop, imgsz)
         if getattr(self, "_scanner_key", None) != key:
             self._scanner = DetectionPredictor(self.model, device=self.device, conf=conf, iou=iou, max_det=max_det, classes=classes,
-                                               agnostic_nms=agnostic_nms, half=half, producer=SpectrogramProducer(self.device))
+                                               agnostic_nms=agnostic_nms, half=half, imgsz=imgsz,
+                                               producer=SpectrogramProducer(self.device, n_fft, hop, imgsz, imgsz))
             self._scanner_key = key
         return self._scanner.scan(open_iq(source), sample_rate, center_freq=center_freq, overlap=overlap, batch=batch, merge=merge,
                                   merge_thres=merge_thres, stride_frames=stride_frames)
@@ -278,4 +325,5 @@ def _device_list(device):
 
 def _hyp_defaults():
     from ..data.dataset import DEFAULT_HYP
-    return dict(DEFAULT_HYP)
+    from ..data.iq_augment import IQ_HYP
+    return {**DEFAULT_HYP, **IQ_HYP}

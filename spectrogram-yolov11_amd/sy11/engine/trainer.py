@@ -248,7 +248,7 @@ class DetectionTrainer:
             rec = {"epoch": epoch, "train_loss": [float(v) for v in tloss] if tloss is not None else None, "metrics": None, "fitness": None}
             if rank0 and val_batches is not None:
                 metrics = DetectionValidator(self.ema.ema if self.ema else self.model, device=self.device,
-                                             half=self.amp)(self.ema.ema if self.ema else self.model, val_batches())
+                                             half=self.amp, producer=self.producer)(self.ema.ema if self.ema else self.model, val_batches())
                 rec["metrics"] = metrics
                 rec["fitness"] = float(metrics.get("fitness", 0.1 * metrics.get("metrics/mAP50(B)", 0.0) + 0.9 * metrics.get("metrics/mAP50-95(B)", 0.0)))
             if rank0 and save_dir:

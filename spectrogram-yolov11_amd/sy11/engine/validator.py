@@ -36,7 +36,7 @@ class DetectionValidator:
 
     # ---- val.py:52-67
     def preprocess(self, batch):
-        img = batch["img"]
+        img = batch.pop("iq") if "iq" in batch else batch["img"]         # an IQ loader's batch carries the samples under "iq"
         if torch.is_complex(img):
             if self.producer is None:
                 raise ValueError("raw IQ input needs a SpectrogramProducer")

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -459,6 +460,54 @@ def stft_windows(db_strip, start, n_frames, out=None):
     fmm = torch.empty((F, 2), dtype=torch.float32, device=db_strip.device)
     call("sy11_stft_windows", F, n_mel, int(n_frames), W, _p(start), _p(db_strip), _p(mm), _p(fmm), _p(img), _stream())
     return img, mm
+
+
+IQ_RECIPE = np.dtype([("dphi", "<u4"), ("phi0", "<u4"), ("gain", "<f4"), ("sigma", "<f4"), ("seed", "<u8"), ("src2", "<u8"), ("off2", "<i8"),
+                      ("dphi2", "<u4"), ("phi02", "<u4"), ("gain2", "<f4"), ("flags", "<u4")])          # sy11_iq_recipe, 56 bytes
+
+
+def iq_recipes(B):
+    """B identity rows of the kernel's recipe table (gain 1, everything else off) as a numpy record array."""
+    rec = np.zeros(B, dtype=IQ_RECIPE)
+    rec["gain"], rec["gain2"] = 1.0, 1.0
+    return rec
+
+
+def iq_gather_augment(srcs, offs, L, rec=None, partners=None, out=None):
+    """One launch: window ``b`` = ``L`` samples of ``srcs[b]`` (a 1-D contiguous complex64 device tensor: a resident capture or a
+    staged copy) from sample ``offs[b]`` (may be odd), through row ``b`` of ``rec`` (``iq_recipes``; None = plain gather) ->
+    (B, L) complex64.  ``partners[b]``: the capture row b's ``off2`` / ``dphi2`` / ``phi02`` / ``gain2`` refer to, or None (no mix; the
+    ``src2`` field is filled in here).  Both windows are bounds-checked against their tensors before anything is launched; the two
+    tables and the recipes travel to the device as ONE small copy."""
+    B = len(srcs)
+    if B == 0 or len(offs) != B or (partners is not None and len(partners) != B) or (rec is not None and (rec.dtype != IQ_RECIPE or rec.shape != (B,))):
+        raise _lib.Sy11Error("iq_gather_augment: need one source, one offset, one recipe row (and one partner or None) per batch row")
+    _need_gpu(*srcs)
+    rec = iq_recipes(B) if rec is None else rec.copy()
+    L = int(L)
+    table = np.empty(B * (16 + IQ_RECIPE.itemsize), dtype=np.uint8)
+    ptr, off = table[:8 * B].view(np.uint64), table[8 * B:16 * B].view(np.int64)
+    for b in range(B):
+        for what, t, o in (("source", srcs[b], int(offs[b])), ("partner", None if partners is None else partners[b], int(rec["off2"][b]))):
+            if t is None:
+                continue
+            if t.dtype != torch.complex64 or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+                raise _lib.Sy11Error(f"iq_gather_augment: {what} {b} must be a 1-D contiguous complex64 device tensor")
+            if o < 0 or o + L > t.shape[0]:
+                raise _lib.Sy11Error(f"iq_gather_augment: {what} {b}: samples [{o}, {o + L}) leave the capture ({t.shape[0]} samples)")
+        ptr[b], off[b] = srcs[b].data_ptr(), int(offs[b])
+        rec["src2"][b] = 0 if partners is None or partners[b] is None else partners[b].data_ptr()
+    table[16 * B:] = rec.view(np.uint8)
+    dev = srcs[0].device
+    if out is not None and (tuple(out.shape) != (B, L) or out.dtype != torch.complex64 or not out.is_contiguous() or out.device != dev):
+        raise _lib.Sy11Error("iq_gather_augment: `out` must be a contiguous complex64 (B, L) tensor on the sources' device")
+    y = out if out is not None else torch.empty((B, L), dtype=torch.complex64, device=dev)
+    t = torch.from_numpy(table).to(dev)
+    base = t.data_ptr()
+    call("sy11_iq_gather_augment", B, L, C.c_void_p(base), C.c_void_p(base + 8 * B), C.c_void_p(base + 16 * B),
+         C.c_void_p(torch.view_as_real(y).data_ptr()), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return y
 
 
 SCAN_METRICS = {"iou": 0, "ios": 1}
