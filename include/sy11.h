@@ -457,6 +457,21 @@ typedef struct sy11_iq_recipe {
 int sy11_iq_gather_augment(int32_t B, int32_t L, const uint64_t* src_ptr, const int64_t* src_off, const sy11_iq_recipe* r,
                            float* out, void* stream);
 
+/* ---- digital down-converter at the front of a scan: mix -> low-pass -> rational resample (spec in DESIGN.md §4) ----
+ *   y[m] = sum_{j < T} taps[phi  j] xm[i0 - j]    i0 = floor((m Q + c) / P)    phi = (m Q + c) mod P
+ *   xm[i] = x[i] e^{j 2 pi frac(i dphi / 2^32)}   x = 0 outside in[]
+ * for the outputs m0 <= m < m0 + M of a capture resampled by P / Q.  taps: DEVICE (P T) f32 polyphase table of a low-pass with
+ * centre tap c at the P-times up-sampled rate (entry [phi j] = h[phi + j P]; sy11/data/resample.py builds it).  in: complex64
+ * samples n0 <= i < n0 + n_in (absolute indices of the capture); the caller guarantees that they cover every sample of the capture
+ * the outputs read - [floor((m0 Q + c) / P) - T + 1   floor(((m0 + M - 1) Q + c) / P)] - and everything outside in[] reads as zero.
+ * The mixer phase (uint32) i * dphi wraps in uint32 arithmetic (exact for every i); the rotation is evaluated in float64 and rounded
+ * to float32 once, per INPUT sample; dphi = 0 skips the mixer.  Every output is one sequential f32 sum over j = 0 .. T - 1, so a value depends on
+ * (m  capture) only, never on the launch shape or on how the caller cut the capture into calls.  P == Q: no filter, out[m] = xm[m]
+ * (in[] must hold the samples m0 .. m0 + M - 1).  P Q <= 4096, 1/64 <= P/Q <= 64, c < P T, M and n_in below 2^31; in / out 8-byte
+ * aligned (in may start at an odd sample of its allocation).  Nothing is launched on an error.                            */
+int sy11_iq_resample(int32_t P, int32_t Q, int32_t T, int32_t c, const float* taps, int64_t n0, int32_t n_in, const float* in,
+                     uint32_t dphi, int64_t m0, int32_t M, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,7 @@ SIGNATURES = {
     "sy11_image_mixup_warp": [_i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _f64, _f64, _i32, _i32, _vp, _i32, _i32,
                               _i32, _i32, _i32, _vp, _vp],
     "sy11_iq_gather_augment": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "sy11_iq_resample": [_i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _u32, _i64, _i32, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],

@@ -176,13 +176,16 @@ class SpectrogramProducer:
         start[w0:w1])``.  ``iq``: an opened capture (``open_iq``; anything with ``iq[lo:hi]`` -> complex64, e.g. an ``np.memmap``
         far larger than device memory); ``start``: first frame of every window (``plan_windows``).  Per chunk the samples its
         windows cover go host -> device through a pinned staging buffer, ONE strip ``logmel`` call transforms every frame once
-        and one ``stft_windows`` call cuts and normalises the windows, so strip memory is bounded by the chunk.  ``out``: an
+        and one ``stft_windows`` call cuts and normalises the windows, so strip memory is bounded by the chunk.  A capture whose
+        slices are device tensors already (it says so with ``yields_device = True``: ``resample.ResampledCapture``) is used as it
+        is, with no staging.  ``out``: an
         optional (chunk_windows, 3, n_mel, n_frames) f32 buffer to write every chunk's images into (valid until the next chunk)."""
         start = np.asarray(start, dtype=np.int64).reshape(-1)
         chunks = plan_chunks(start, chunk_windows, self.n_fft, self.hop, self.n_frames)
         on_device = isinstance(iq, torch.Tensor) and iq.is_cuda
+        yields_device = bool(getattr(iq, "yields_device", False))        # e.g. a ResampledCapture: iq[lo:hi] is a device tensor already
         stage, copied = None, None
-        if chunks and not on_device:
+        if chunks and not on_device and not yields_device:
             stage = torch.empty((max(hi - lo for _, _, lo, hi in chunks),), dtype=torch.complex64).pin_memory()
         for w0, w1, lo, hi in chunks:
             L = hi - lo
@@ -190,6 +193,13 @@ class SpectrogramProducer:
                 if hi > iq.shape[0]:
                     raise ValueError(f"the capture ends before sample {hi}")
                 dev_iq = iq[lo:hi].contiguous()
+            elif yields_device:
+                dev_iq = iq[lo:hi]
+                if not (isinstance(dev_iq, torch.Tensor) and dev_iq.is_cuda and dev_iq.dtype == torch.complex64):
+                    raise ValueError("a capture that declares `yields_device` must return complex64 device tensors")
+                if dev_iq.shape != (L,):
+                    raise ValueError(f"the capture ends before sample {hi} (got {dev_iq.shape[0]} of {L} samples from {lo})")
+                dev_iq = dev_iq.contiguous()
             else:
                 if copied is not None:
                     copied.synchronize()                       # the staging buffer is free once the previous chunk's copy is done

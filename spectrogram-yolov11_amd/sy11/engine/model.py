@@ -282,16 +282,22 @@ class YOLO:
     __call__ = predict
 
     def scan(self, source, sample_rate, center_freq=0.0, conf=0.25, iou=0.7, overlap=0.5, batch=64, merge="ios", merge_thres=0.5,
-             max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None, n_fft=1024, hop=256, imgsz=640):
+             max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None, n_fft=1024, hop=256, imgsz=640,
+             resample_to=None, tune_to=None):
         """Detect over a long IQ capture (no reference counterpart) -> ``ScanResults`` with boxes in strip frames / image rows and
         in seconds / Hz.  ``source``: a 1-D complex64 tensor or ndarray, a ``.npy`` of complex64, or a raw interleaved-float32
         file (``.cf32`` / ``.fc32`` / ``.iq``), opened with ``np.memmap`` and read chunk by chunk.  ``sample_rate`` in Hz,
         ``center_freq`` the RF centre the capture was tuned to.  See ``DetectionPredictor.scan`` for ``overlap`` / ``merge``.
         ``n_fft`` / ``hop`` / ``imgsz`` (n_frames = n_mel) select the transform; a model trained from IQ captures records its own in
-        the checkpoint, and a scan with another one warns (its results are those of the transform asked for)."""
+        the checkpoint, and a scan with another one warns (its results are those of the transform asked for).
+        ``resample_to`` (Hz, or ``"model"`` = the rate, and the centre if there is one, that the checkpoint records) / ``tune_to``
+        (Hz): resample and retune the capture on the GPU first, so that a recording taken at another rate or tuning meets the
+        transform the model knows (``DetectionPredictor.scan``); boxes stay in seconds of the capture and absolute Hz."""
         from ..data.spectrogram import SpectrogramProducer, open_iq
-        from .predictor import DetectionPredictor
+        from .predictor import DetectionPredictor, plan_scan_ddc
         trained = (self.ckpt or {}).get("train_args") or {}
+        if resample_to is not None or tune_to is not None:    # argument errors come first, before anything touches the device
+            resample_to, tune_to = plan_scan_ddc(sample_rate, center_freq, resample_to, tune_to, trained), None
         if "n_fft" in trained and (trained["n_fft"], trained["hop"], trained.get("imgsz", imgsz)) != (n_fft, hop, imgsz):
             import warnings                                   # the results are those of the transform asked for, as they always were
             warnings.warn(f"scan(n_fft={n_fft}, hop={hop}, imgsz={imgsz}) differs from the transform this model was trained on "
@@ -302,8 +308,9 @@ class YOLO:
                                                agnostic_nms=agnostic_nms, half=half, imgsz=imgsz,
                                                producer=SpectrogramProducer(self.device, n_fft, hop, imgsz, imgsz))
             self._scanner_key = key
+        self._scanner.trained = trained
         return self._scanner.scan(open_iq(source), sample_rate, center_freq=center_freq, overlap=overlap, batch=batch, merge=merge,
-                                  merge_thres=merge_thres, stride_frames=stride_frames)
+                                  merge_thres=merge_thres, stride_frames=stride_frames, resample_to=resample_to, tune_to=tune_to)
 
 
 def _device_list(device):

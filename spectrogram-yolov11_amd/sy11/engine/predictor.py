@@ -58,11 +58,14 @@ class ScanResults:
     """Detections of a long-capture scan (``DetectionPredictor.scan``), one row per box:
     ``boxes`` (n, 6) float64 [X1, y1, X2, y2, conf, cls] — X in strip frames (window start + window-local x), y in image rows;
     ``window`` (n,) int64 the window a box was found in; ``tf`` (n, 4) float64 [t0_s, f_lo_hz, t1_s, f_hi_hz];
-    ``start`` (W,) int64 first frame of every window."""
+    ``start`` (W,) int64 first frame of every window.  After a resampled / retuned scan ``sample_rate`` / ``center_freq`` are those
+    of the DDC's output (frames, ``boxes`` and ``start`` count its samples), ``tf`` stays in seconds of the original capture and in
+    absolute Hz, and ``resample`` is the plan that was used."""
 
-    def __init__(self, boxes, window, tf, names, start, sample_rate, center_freq):
+    def __init__(self, boxes, window, tf, names, start, sample_rate, center_freq, resample=None):
         self.boxes, self.window, self.tf, self.names = boxes, window, tf, names
         self.start, self.sample_rate, self.center_freq = start, sample_rate, center_freq
+        self.resample = resample                            # the ResamplePlan of a resampled / retuned scan, else None
 
     def __len__(self):
         return self.boxes.shape[0]
@@ -83,6 +86,7 @@ class DetectionPredictor:
             from . import enable_graphs
             enable_graphs(self.model)
         self.imgsz = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+        self.trained = None                                 # the checkpoint's train_args (YOLO.scan sets it): what "model" means in scan
         self._lock = threading.Lock()                       # predictor.py:115: one inference at a time per predictor
 
     def pre_transform(self, im, out_dtype=None):
@@ -144,7 +148,7 @@ class DetectionPredictor:
 
     @torch.no_grad()
     def scan(self, iq, sample_rate, center_freq=0.0, overlap=0.5, batch=64, merge="ios", merge_thres=0.5, stride_frames=None,
-             start=None):
+             start=None, resample_to=None, tune_to=None):
         """Run the model over a capture of any length -> ``ScanResults``.  ``iq``: what ``sy11.data.spectrogram.open_iq`` returns
         (1-D complex64 samples: array, tensor or ``np.memmap``).  Windows come from ``plan_windows(len(iq), overlap | stride_frames)``
         (or ``start``); per chunk of ``batch`` windows: the producer's strip images -> ``inference`` (graph replay for full chunks,
@@ -152,7 +156,13 @@ class DetectionPredictor:
         the last chunk ONE seam merge (``ops.scan_merge``) suppresses, in strip coordinates, the boxes that overlapping windows
         found twice: ``merge`` = "ios" (intersection over the smaller area: a box cut by a window edge matches its full twin from
         the neighbouring window, which IoU does not), "iou", or None for the unmerged rows.  ``merge_thres`` = 0.5 for "ios" is a
-        default chosen by judgement, not a measured optimum."""
+        default chosen by judgement, not a measured optimum.
+
+        ``resample_to`` / ``tune_to`` put a DDC (``sy11.data.resample``) in front: the capture is low-passed and resampled to
+        ``resample_to`` Hz and ``tune_to`` Hz becomes the new centre, chunk by chunk on the device.  ``"model"`` stands for the rate
+        (and, for ``tune_to``, the centre) the checkpoint records; a ready ``ResamplePlan`` (``plan_scan_ddc``) is taken as it is.
+        The results then carry the output rate, the centre really tuned to (the shift is a whole number of 2^-32 cycles per
+        sample) and the plan; seconds and Hz stay those of the capture."""
         from .. import ops as kops
         from ..data import spectrogram as sp
         if self.producer is None:
@@ -160,6 +170,13 @@ class DetectionPredictor:
         if merge not in (None, "ios", "iou"):
             raise ValueError(f"merge must be 'ios', 'iou' or None, got {merge!r}")
         p = self.producer
+        plan = None
+        if resample_to is not None or tune_to is not None:
+            from ..data.resample import ResampledCapture, ResamplePlan
+            plan = resample_to if isinstance(resample_to, ResamplePlan) else plan_scan_ddc(sample_rate, center_freq, resample_to, tune_to,
+                                                                                           self.trained)
+            iq = ResampledCapture(iq, plan, self.device)
+            sample_rate, center_freq = plan.fs_out, float(center_freq) + plan.shift_hz
         if (p.n_mel, p.n_frames) != tuple(self.imgsz):
             raise ValueError(f"the producer's {p.n_mel} x {p.n_frames} images do not match imgsz={self.imgsz}")
         if start is None:
@@ -191,7 +208,34 @@ class DetectionPredictor:
         boxes[:, 0] += off
         boxes[:, 2] += off
         tf = scan_boxes_to_tf(boxes, sample_rate, center_freq, p)
-        return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq))
+        return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq), plan)
+
+
+def plan_scan_ddc(sample_rate, center_freq, resample_to=None, tune_to=None, trained=None):
+    """The ``ResamplePlan`` of ``scan(..., resample_to, tune_to)``; every argument error of the two keywords is raised here.
+    ``trained``: the checkpoint's ``train_args`` (what ``"model"`` refers to)."""
+    from ..data.resample import plan_resample
+    trained = trained or {}
+    if isinstance(resample_to, str) or isinstance(tune_to, str):
+        if any(isinstance(v, str) and v != "model" for v in (resample_to, tune_to)):
+            raise ValueError(f"resample_to / tune_to take Hz or 'model', got {resample_to!r} / {tune_to!r}")
+        if resample_to == "model":
+            if not trained.get("sample_rate"):
+                raise ValueError("resample_to='model': this checkpoint records no sample_rate (it was not trained from IQ captures)")
+            resample_to = float(trained["sample_rate"])
+            if tune_to is None and trained.get("center_freq"):       # a recorded centre of 0 is "baseband, untuned": nothing to tune to
+                tune_to = "model"
+        if tune_to == "model":
+            if "center_freq" not in trained:
+                raise ValueError("tune_to='model': this checkpoint records no center_freq")
+            tune_to = float(trained["center_freq"])
+    fs_in = sample_rate
+    fs_out = fs_in if resample_to is None else resample_to
+    shift = 0.0 if tune_to is None else float(tune_to) - float(center_freq)
+    if shift != 0.0 and abs(shift) + float(fs_out) / 2 > float(fs_in) / 2:
+        raise ValueError(f"the kept band {float(tune_to)!r} +- {float(fs_out) / 2!r} Hz is not inside the capture's "
+                         f"{float(center_freq)!r} +- {float(fs_in) / 2!r} Hz")
+    return plan_resample(fs_in, fs_out, shift)
 
 
 def scan_boxes_to_tf(boxes, sample_rate, center_freq, producer):
