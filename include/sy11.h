@@ -472,6 +472,23 @@ int sy11_iq_gather_augment(int32_t B, int32_t L, const uint64_t* src_ptr, const 
 int sy11_iq_resample(int32_t P, int32_t Q, int32_t T, int32_t c, const float* taps, int64_t n0, int32_t n_in, const float* in,
                      uint32_t dphi, int64_t m0, int32_t M, float* out, void* stream);
 
+/* ---- polyphase analysis filter bank: all K bands of a capture from one read of its samples (spec in DESIGN.md §4) ----
+ *   y_k[m] = sum_n h[n] x[m D + c - n] e^{-j 2 pi k (m D + c - n) / K}    x = 0 outside in[]
+ *          = sum_{r < K} e^{-j 2 pi k r / K} v_m[r]    v_m[r] = sum_{i = r (mod K)} h[m D + c - i] x[i]
+ * for the time steps m0 <= m < m0 + M and every channel 0 <= k < K: channel k is sy11_iq_resample with P = 1, Q = D and
+ * dphi = (-k 2^32 / K) mod 2^32.  K a power of two in [2, 64]; D = K (critically sampled) or K / 2 (2x oversampled); taps: DEVICE N =
+ * 32 D + 1 f32 of the low-pass of the DDC for 1 / D, centre c = 16 D; twiddle: DEVICE K / 2 complex64 e^{-j 2 pi t / K} (built on the
+ * host in float64, rounded once).  in: complex64 samples n0 <= i < n0 + n_in (absolute indices i of the capture, which also fix the
+ * residue r = i mod K: a chunk cut anywhere gives the same values); the caller guarantees that they cover every sample of the
+ * capture the outputs read - [m0 D + c - N + 1   (m0 + M - 1) D + c] - and everything outside in[] reads as zero.
+ * out[k out_stride + (m - m0)]: complex64, channel-major, out_stride >= M complex samples between channels.  Every v_m[r] is one
+ * sequential f32 sum in ascending tap index and the K-point FFT runs in one fixed order (radix-2 decimation in frequency), so a value
+ * depends on (k  m  capture) only, never on the tile, the launch shape or on how the caller cut the capture into calls.  n0, m0 >= 0,
+ * m0 < 2^48, M and n_in positive and below 2^31; in / out 8-byte aligned (in may start at an odd sample of its allocation).
+ * Nothing is launched on an error.                                                                                        */
+int sy11_iq_channelize(int32_t K, int32_t D, int32_t N, int32_t c, const float* taps, const float* twiddle, int64_t n0, int32_t n_in,
+                       const float* in, int64_t m0, int32_t M, int64_t out_stride, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

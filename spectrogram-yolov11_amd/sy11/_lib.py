@@ -114,6 +114,7 @@ SIGNATURES = {
                               _i32, _i32, _i32, _vp, _vp],
     "sy11_iq_gather_augment": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "sy11_iq_resample": [_i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _u32, _i64, _i32, _vp, _vp],
+    "sy11_iq_channelize": [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],

@@ -283,7 +283,7 @@ class YOLO:
 
     def scan(self, source, sample_rate, center_freq=0.0, conf=0.25, iou=0.7, overlap=0.5, batch=64, merge="ios", merge_thres=0.5,
              max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None, n_fft=1024, hop=256, imgsz=640,
-             resample_to=None, tune_to=None):
+             resample_to=None, tune_to=None, channels=None, oversample=2, select=None):
         """Detect over a long IQ capture (no reference counterpart) -> ``ScanResults`` with boxes in strip frames / image rows and
         in seconds / Hz.  ``source``: a 1-D complex64 tensor or ndarray, a ``.npy`` of complex64, or a raw interleaved-float32
         file (``.cf32`` / ``.fc32`` / ``.iq``), opened with ``np.memmap`` and read chunk by chunk.  ``sample_rate`` in Hz,
@@ -292,11 +292,18 @@ class YOLO:
         the checkpoint, and a scan with another one warns (its results are those of the transform asked for).
         ``resample_to`` (Hz, or ``"model"`` = the rate, and the centre if there is one, that the checkpoint records) / ``tune_to``
         (Hz): resample and retune the capture on the GPU first, so that a recording taken at another rate or tuning meets the
-        transform the model knows (``DetectionPredictor.scan``); boxes stay in seconds of the capture and absolute Hz."""
+        transform the model knows (``DetectionPredictor.scan``); boxes stay in seconds of the capture and absolute Hz.
+        ``channels`` (K, a ``ChannelPlan`` or ``"model"``) / ``oversample`` / ``select``: split a wideband capture into K bands with
+        a polyphase filter bank on the GPU and scan every selected band from one read of the capture; the rows carry their band in
+        ``ScanResults.channel`` (``DetectionPredictor.scan``)."""
         from ..data.spectrogram import SpectrogramProducer, open_iq
         from .predictor import DetectionPredictor, plan_scan_ddc
         trained = (self.ckpt or {}).get("train_args") or {}
-        if resample_to is not None or tune_to is not None:    # argument errors come first, before anything touches the device
+        if channels is not None:                              # argument errors come first, before anything touches the device
+            from ..data.channelize import plan_scan_channels
+            channels, select = plan_scan_channels(sample_rate, channels, oversample, select, trained, resample_to, tune_to)
+            oversample = channels.oversample
+        elif resample_to is not None or tune_to is not None:
             resample_to, tune_to = plan_scan_ddc(sample_rate, center_freq, resample_to, tune_to, trained), None
         if "n_fft" in trained and (trained["n_fft"], trained["hop"], trained.get("imgsz", imgsz)) != (n_fft, hop, imgsz):
             import warnings                                   # the results are those of the transform asked for, as they always were
@@ -310,7 +317,8 @@ class YOLO:
             self._scanner_key = key
         self._scanner.trained = trained
         return self._scanner.scan(open_iq(source), sample_rate, center_freq=center_freq, overlap=overlap, batch=batch, merge=merge,
-                                  merge_thres=merge_thres, stride_frames=stride_frames, resample_to=resample_to, tune_to=tune_to)
+                                  merge_thres=merge_thres, stride_frames=stride_frames, resample_to=resample_to, tune_to=tune_to,
+                                  channels=channels, oversample=oversample, select=select)
 
 
 def _device_list(device):

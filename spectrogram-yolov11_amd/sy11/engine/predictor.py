@@ -60,12 +60,16 @@ class ScanResults:
     ``window`` (n,) int64 the window a box was found in; ``tf`` (n, 4) float64 [t0_s, f_lo_hz, t1_s, f_hi_hz];
     ``start`` (W,) int64 first frame of every window.  After a resampled / retuned scan ``sample_rate`` / ``center_freq`` are those
     of the DDC's output (frames, ``boxes`` and ``start`` count its samples), ``tf`` stays in seconds of the original capture and in
-    absolute Hz, and ``resample`` is the plan that was used."""
+    absolute Hz, and ``resample`` is the plan that was used.  After a channelised scan ``channel`` (n,) int64 is the band every
+    row was found in and ``channelizer`` the ``ChannelPlan``: ``sample_rate`` is the bands' rate (frames, ``boxes`` and ``start`` count
+    a band's samples; all bands share ``start``), ``center_freq`` stays the capture's (band k is centred at ``center_freq +
+    channelizer.offset_hz[k]``), ``tf`` is in seconds of the capture and absolute Hz; rows are ordered by channel."""
 
-    def __init__(self, boxes, window, tf, names, start, sample_rate, center_freq, resample=None):
+    def __init__(self, boxes, window, tf, names, start, sample_rate, center_freq, resample=None, channel=None, channelizer=None):
         self.boxes, self.window, self.tf, self.names = boxes, window, tf, names
         self.start, self.sample_rate, self.center_freq = start, sample_rate, center_freq
         self.resample = resample                            # the ResamplePlan of a resampled / retuned scan, else None
+        self.channel, self.channelizer = channel, channelizer       # a channelised scan's band per row and its ChannelPlan, else None
 
     def __len__(self):
         return self.boxes.shape[0]
@@ -148,7 +152,7 @@ class DetectionPredictor:
 
     @torch.no_grad()
     def scan(self, iq, sample_rate, center_freq=0.0, overlap=0.5, batch=64, merge="ios", merge_thres=0.5, stride_frames=None,
-             start=None, resample_to=None, tune_to=None):
+             start=None, resample_to=None, tune_to=None, channels=None, oversample=2, select=None):
         """Run the model over a capture of any length -> ``ScanResults``.  ``iq``: what ``sy11.data.spectrogram.open_iq`` returns
         (1-D complex64 samples: array, tensor or ``np.memmap``).  Windows come from ``plan_windows(len(iq), overlap | stride_frames)``
         (or ``start``); per chunk of ``batch`` windows: the producer's strip images -> ``inference`` (graph replay for full chunks,
@@ -162,7 +166,15 @@ class DetectionPredictor:
         ``resample_to`` Hz and ``tune_to`` Hz becomes the new centre, chunk by chunk on the device.  ``"model"`` stands for the rate
         (and, for ``tune_to``, the centre) the checkpoint records; a ready ``ResamplePlan`` (``plan_scan_ddc``) is taken as it is.
         The results then carry the output rate, the centre really tuned to (the shift is a whole number of 2^-32 cycles per
-        sample) and the plan; seconds and Hz stay those of the capture."""
+        sample) and the plan; seconds and Hz stay those of the capture.
+
+        ``channels`` puts a polyphase filter bank (``sy11.data.channelize``) in front instead and scans every band of a wideband
+        capture from one read of it: K (a power of two, 2 .. 64), a ready ``ChannelPlan``, or ``"model"`` (K = ``oversample`` x the
+        capture's rate over the checkpoint's, which must be a power of two).  ``oversample`` = 2 lets neighbouring bands share half
+        their width, so an emission cut by one band's edge is whole in the next; ``select`` = the bands to scan (default: all but
+        K/2, which wraps round the capture's edge).  Per chunk there is ONE channelise launch, then the usual steps per band; after
+        the per-band seam merges a cross-band merge (``channelize.merge_channels``, in seconds / Hz) runs when ``oversample`` is 2
+        and ``merge`` is not None.  ``channels`` excludes ``resample_to`` / ``tune_to``."""
         from .. import ops as kops
         from ..data import spectrogram as sp
         if self.producer is None:
@@ -170,6 +182,9 @@ class DetectionPredictor:
         if merge not in (None, "ios", "iou"):
             raise ValueError(f"merge must be 'ios', 'iou' or None, got {merge!r}")
         p = self.producer
+        if channels is not None:
+            return self._scan_channels(iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start,
+                                       resample_to, tune_to, channels, oversample, select)
         plan = None
         if resample_to is not None or tune_to is not None:
             from ..data.resample import ResampledCapture, ResamplePlan
@@ -209,6 +224,72 @@ class DetectionPredictor:
         boxes[:, 2] += off
         tf = scan_boxes_to_tf(boxes, sample_rate, center_freq, p)
         return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq), plan)
+
+    def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
+                       tune_to, channels, oversample, select):
+        """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over
+        one ``ChannelizedCapture``, whose first slice of a chunk is the chunk's one channelise launch and whose other slices are
+        rows of that block; every band's chunk is consumed (inference + NMS) before the next band's is produced, so one image
+        buffer serves all of them."""
+        from .. import ops as kops
+        from ..data import spectrogram as sp
+        from ..data.channelize import ChannelizedCapture, merge_channels, plan_scan_channels
+        p = self.producer
+        plan, select = plan_scan_channels(sample_rate, channels, oversample, select, self.trained, resample_to, tune_to)
+        if (p.n_mel, p.n_frames) != tuple(self.imgsz):
+            raise ValueError(f"the producer's {p.n_mel} x {p.n_frames} images do not match imgsz={self.imgsz}")
+        cap = ChannelizedCapture(iq, plan, self.device)
+        if start is None:
+            start = sp.plan_windows(len(cap), overlap, stride_frames, p.n_fft, p.hop, p.n_frames)
+        start = np.asarray(start, dtype=np.int64).reshape(-1)
+        a = self.args
+        fs_out = plan.fs_out
+        rows, wins = {k: [] for k in select}, {k: [] for k in select}
+        out_b, out_w, out_c = [], [], []
+        with self._lock:
+            buf = torch.empty((min(batch, max(start.size, 1)), 3, p.n_mel, p.n_frames), dtype=torch.float32, device=self.device)
+            gens = [(k, p.scan(cap.channel(k), start, chunk_windows=batch, out=buf)) for k in select]
+            w0 = 0
+            for _ in sp.plan_chunks(start, batch, p.n_fft, p.hop, p.n_frames):
+                n_st = 0
+                for k, gen in gens:
+                    img, st = next(gen)
+                    preds = ops.non_max_suppression(self.inference(img), a["conf"], a["iou"], classes=a["classes"],
+                                                    agnostic=a["agnostic_nms"], max_det=a["max_det"])
+                    for j, pr in enumerate(preds):
+                        pr = pr[:, :6].float().clone()
+                        ops.clip_boxes(pr[:, :4], img.shape[2:])
+                        rows[k].append(pr)
+                        wins[k].append(torch.full((pr.shape[0],), w0 + j, dtype=torch.int32, device=pr.device))
+                    n_st = len(st)
+                w0 += n_st
+            for k in select:
+                r = torch.cat(rows[k]) if rows[k] else torch.zeros((0, 6), dtype=torch.float32, device=self.device)
+                w = torch.cat(wins[k]) if wins[k] else torch.zeros((0,), dtype=torch.int32, device=self.device)
+                if merge is not None and r.shape[0]:
+                    keep = kops.scan_merge(w, r[:, :4].contiguous(), r[:, 4].contiguous(), r[:, 5].to(torch.int32), start, p.n_frames,
+                                           metric=merge, thres=merge_thres, agnostic=a["agnostic_nms"])
+                    r, w = r[keep], w[keep]
+                out_b.append(r.cpu())
+                out_w.append(w.cpu().to(torch.int64))
+                out_c.append(torch.full((r.shape[0],), k, dtype=torch.int64))
+        tfs = []
+        for k, r, w in zip(select, out_b, out_w):
+            b = r.to(torch.float64)
+            off = torch.from_numpy(start)[w].to(torch.float64)
+            b[:, 0] += off
+            b[:, 2] += off
+            tfs.append(scan_boxes_to_tf(b, fs_out, float(center_freq) + float(plan.offset_hz[k]), p))
+        boxes = torch.cat([r.to(torch.float64) for r in out_b])
+        wins, chan, tf = torch.cat(out_w), torch.cat(out_c), torch.cat(tfs)
+        off = torch.from_numpy(start)[wins].to(torch.float64)
+        boxes[:, 0] += off
+        boxes[:, 2] += off
+        if merge is not None and plan.oversample == 2 and boxes.shape[0]:
+            keep = torch.from_numpy(merge_channels(tf.numpy(), boxes[:, 4].numpy(), boxes[:, 5].numpy(), chan.numpy(), merge, merge_thres,
+                                                   a["agnostic_nms"]))
+            boxes, wins, chan, tf = boxes[keep], wins[keep], chan[keep], tf[keep]
+        return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(fs_out), float(center_freq), None, chan, plan)
 
 
 def plan_scan_ddc(sample_rate, center_freq, resample_to=None, tune_to=None, trained=None):

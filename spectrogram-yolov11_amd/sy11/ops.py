@@ -547,6 +547,40 @@ def iq_resample(x, plan, n0, m0, M, out=None, n_total=None):
     return y
 
 
+def iq_channelize(x, plan, n0, m0, M, out=None, n_total=None):
+    """One launch of the polyphase filter bank (sy11_iq_channelize): time steps ``[m0, m0 + M)`` of every channel of the capture
+    under ``plan`` (``sy11.data.channelize.plan_channels``) -> (K, M) complex64, channel-major.  ``x``, ``n0`` and ``n_total`` as in
+    ``iq_resample``: ``x`` holds the capture's samples ``[n0, n0 + len(x))`` (its base may be an odd sample of a larger tensor) and
+    must cover ``plan.support(m0, m0 + M)`` clipped to the capture; samples outside the capture are zeros."""
+    _need_gpu(x, out)
+    n0, m0, M = int(n0), int(m0), int(M)
+    if x.dtype != torch.complex64 or x.dim() != 1 or not x.is_contiguous() or x.shape[0] == 0:
+        raise _lib.Sy11Error("iq_channelize: x must be a non-empty 1-D contiguous complex64 device tensor")
+    n_in = x.shape[0]
+    if n_total is None:
+        if n0 != 0:
+            raise _lib.Sy11Error("iq_channelize: n0 != 0 needs the capture's length (n_total)")
+        n_total = n_in
+    n_total = int(n_total)
+    if n0 < 0 or n0 + n_in > n_total:
+        raise _lib.Sy11Error(f"iq_channelize: samples [{n0}, {n0 + n_in}) leave the capture ({n_total} samples)")
+    if M <= 0 or m0 < 0 or m0 + M > plan.n_out(n_total):
+        raise _lib.Sy11Error(f"iq_channelize: time steps [{m0}, {m0 + M}) are not among the capture's {plan.n_out(n_total)}")
+    if M >= 2 ** 31 or n_in >= 2 ** 31:
+        raise _lib.Sy11Error(f"iq_channelize: M = {M} and n_in = {n_in} must stay below 2^31 per call")
+    a, b = plan.support(m0, m0 + M)
+    a, b = max(a, 0), min(b, n_total)
+    if a < n0 or b > n0 + n_in:
+        raise _lib.Sy11Error(f"iq_channelize: time steps [{m0}, {m0 + M}) read samples [{a}, {b}); x holds [{n0}, {n0 + n_in})")
+    if out is not None and (tuple(out.shape) != (plan.K, M) or out.dtype != torch.complex64 or not out.is_contiguous() or out.device != x.device):
+        raise _lib.Sy11Error("iq_channelize: `out` must be a contiguous complex64 (K, M) tensor on x's device")
+    y = out if out is not None else torch.empty((plan.K, M), dtype=torch.complex64, device=x.device)
+    taps, twiddle = plan.on(x.device)
+    call("sy11_iq_channelize", plan.K, plan.D, plan.N, plan.c, _p(taps), C.c_void_p(torch.view_as_real(twiddle).data_ptr()), n0, n_in,
+         C.c_void_p(torch.view_as_real(x).data_ptr()), m0, M, M, C.c_void_p(torch.view_as_real(y).data_ptr()), _stream())
+    return y
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
