@@ -489,6 +489,35 @@ int sy11_iq_resample(int32_t P, int32_t Q, int32_t T, int32_t c, const float* ta
 int sy11_iq_channelize(int32_t K, int32_t D, int32_t N, int32_t c, const float* taps, const float* twiddle, int64_t n0, int32_t n_in,
                        const float* in, int64_t m0, int32_t M, int64_t out_stride, float* out, void* stream);
 
+/* ---- extraction: every detection of a scan as baseband IQ, all of them in one launch (spec in DESIGN.md §4) ----
+ *   out[out_off + (m - m0)] = sum_{j < T} taps_D[j] xm[m D + 16 D - j]    T = 32 D + 1    D = 2^log2d
+ *   xm[i] = x[i] e^{j 2 pi frac(i dphi / 2^32)}                             x = 0 outside in[]
+ * for the outputs m0 <= m < m0 + M of every segment: sy11_iq_resample with P = 1, Q = D, c = 16 D, the same table and the same mixer,
+ * bit for bit (one sequential f32 sum over j = 0 .. T - 1 per output).  log2d = 0: no filter, out = xm (the DDC's mixer).  A segment is a
+ * clip or a piece of one; output m of a segment sits on capture sample m D.
+ * taps: DEVICE f32, the tables of D = 1, 2 .. 64 one after the other, each padded to a multiple of 4 floats: D = 1 is the single tap
+ * 1.0 at float 0, D = 2^l >= 2 is the low-pass of the DDC for 1 / D (32 D + 1 taps) at float 32 D - 64 + 4 l; 4060 floats in all
+ * (sy11/data/extract.py builds it).  seg: DEVICE n_seg segments; tile: DEVICE n_tile pairs (segment, first output relative to its m0),
+ * one per workgroup, first a multiple of sy11_iq_extract_tile(log2d) - every output belongs to the tile that starts at or before it.
+ * seg_host / tile_host: HOST copies of the two tables; they are checked entry by entry before anything is launched: no segment may
+ * read samples outside in[] - [(m0 - 16) D   (m0 + M + 15) D] clipped to the capture [0  n_total), or [m0  m0 + M) for D = 1 - or write
+ * outside out[0  out_len), and every output must lie on the capture ((m0 + M - 1) D < n_total).  in: complex64 samples n0 <= i < n0 +
+ * n_in (absolute indices of the capture; in may start at an odd sample of its allocation); out: out_len complex64 samples.  A value
+ * depends on (m  D  dphi  capture) only, never on the tile, the segment or how the caller cut the capture into calls.
+ * Nothing is launched on an error.                                                                                      */
+typedef struct sy11_iq_segment {
+  int64_t m0;                  /* first output (absolute index on the grid of decimation D: capture sample m0 D)   */
+  int64_t out_off;             /* first complex64 sample of the segment in out                                     */
+  int32_t M;                   /* number of outputs                                                                */
+  int32_t log2d;               /* log2 of the decimation, 0 .. 6                                                   */
+  uint32_t dphi;               /* mixer step per input sample, in 2^-32 cycles                                     */
+  int32_t reserved;            /* 0                                                                                */
+} sy11_iq_segment;
+int32_t sy11_iq_extract_tile(int32_t log2d);      /* outputs per workgroup at decimation 2^log2d (0: log2d out of range) */
+int sy11_iq_extract(int32_t n_seg, const sy11_iq_segment* seg_host, const sy11_iq_segment* seg, int32_t n_tile,
+                    const int32_t* tile_host, const int32_t* tile, const float* taps, int64_t n_total, int64_t n0, int32_t n_in,
+                    const float* in, int64_t out_len, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

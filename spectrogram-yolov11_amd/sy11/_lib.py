@@ -49,6 +49,13 @@ class IqRecipe(C.Structure):
 
 IQ_CONJ, IQ_CONJ2 = 1, 2
 
+
+class IqSegment(C.Structure):
+    """sy11_iq_segment: one clip, or one piece of a clip, of sy11_iq_extract (include/sy11.h)."""
+    _fields_ = [("m0", C.c_int64), ("out_off", C.c_int64), ("M", C.c_int32), ("log2d", C.c_int32), ("dphi", C.c_uint32),
+                ("reserved", C.c_int32)]
+
+
 _vp, _i32, _i64, _f32, _f64, _u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32
 _dp = C.POINTER(ConvDesc)
 _bp = C.POINTER(BnTail)
@@ -115,6 +122,7 @@ SIGNATURES = {
     "sy11_iq_gather_augment": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "sy11_iq_resample": [_i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _u32, _i64, _i32, _vp, _vp],
     "sy11_iq_channelize": [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _vp, _vp],
+    "sy11_iq_extract": [_i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],
@@ -133,6 +141,7 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_nms_batched_workspace_bytes": ([_i32, _vp], C.c_size_t),
          "sy11_scan_merge_workspace_bytes": ([_i32, _i32], C.c_size_t),
          "sy11_attention_workspace_bytes": ([_i32, _i32, _i32], C.c_size_t),
+         "sy11_iq_extract_tile": ([_i32], C.c_int32),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}
 
 _lib = None

@@ -25,6 +25,11 @@ import torch
 
 ZERO_CROSSINGS = 16          # Z: one-sided length of the prototype in zero crossings of the sinc
 KAISER_BETA = 8.0
+# The part of a decimated band that is clean: a property of prototype(1, D) above (Z = 16, beta = 8), not a knob.  In float64, for
+# every D = 2 .. 64, its response stays within 0.01 dB up to 0.427 fs_out and is at or below -80 dB from 0.5795 fs_out upward, so
+# whatever folds into |f| <= 0.42 fs_out (from 0.58 fs_out and beyond) is at least 80 dB down: 0.84 fs_out of every decimated band
+# is flat and alias-free (tests/test_extract_cpu.py pins both figures; sy11/data/extract.py picks D with it).
+USABLE_BAND = 0.84
 MAX_PQ = 4096
 MAX_RATIO = 64
 

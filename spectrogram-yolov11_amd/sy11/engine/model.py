@@ -320,6 +320,14 @@ class YOLO:
                                   merge_thres=merge_thres, stride_frames=stride_frames, resample_to=resample_to, tune_to=tune_to,
                                   channels=channels, oversample=oversample, select=select)
 
+    def extract(self, source, results, sample_rate, center_freq=0.0, rows=None, pad_t=0.0, pad_f=0.1, decimate="auto", chunk_samples=1 << 24):
+        """Take every detection of ``results`` (what ``scan`` returned for this capture) out of the recording as baseband IQ ->
+        ``sy11.data.extract.Extraction`` (``DetectionPredictor.extract``).  ``source`` as in ``scan``; ``sample_rate`` / ``center_freq`` are
+        the capture's own, also after ``scan(resample_to=)`` or ``scan(channels=)``."""
+        from ..data.extract import extract_results
+        from ..data.spectrogram import open_iq
+        return extract_results(open_iq(source), results, sample_rate, center_freq, self.device, rows, pad_t, pad_f, decimate, chunk_samples)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

@@ -225,6 +225,19 @@ class DetectionPredictor:
         tf = scan_boxes_to_tf(boxes, sample_rate, center_freq, p)
         return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq), plan)
 
+    def extract(self, iq, results, sample_rate, center_freq=0.0, rows=None, pad_t=0.0, pad_f=0.1, decimate="auto", chunk_samples=1 << 24):
+        """Every detection of ``results`` (a ``ScanResults`` of this capture) as baseband IQ -> ``sy11.data.extract.Extraction``: per row
+        the band of the box (widened by ``pad_f`` on both sides) is shifted to 0 Hz, low-passed, decimated by a power of two and cut to
+        the box's time span (widened by ``pad_t`` seconds), all clips of a staged chunk in ONE launch (``csrc/extract.hip``).  ``iq``: what
+        ``open_iq`` returns.  ``sample_rate`` / ``center_freq`` are the CAPTURE's own, always passed explicitly: after a resampled or
+        channelised scan ``results.sample_rate`` is the output rate, while ``results.tf`` — the only thing read here — is in seconds
+        and absolute Hz of the capture, so extraction works the same behind ``scan``, ``scan(resample_to=)`` and ``scan(channels=)``.
+        ``rows``: the rows to extract (default: all); ``decimate``: "auto" (the largest power of two <= 64 that keeps the padded band
+        inside the flat, alias-free 84 % of the output rate) or one power of two for all rows.  Argument errors are ``ValueError``s
+        raised before anything touches the device; an empty ``results`` gives an empty ``Extraction`` with no launch."""
+        from ..data.extract import extract_results
+        return extract_results(iq, results, sample_rate, center_freq, self.device, rows, pad_t, pad_f, decimate, chunk_samples)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

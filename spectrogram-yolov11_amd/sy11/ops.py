@@ -581,6 +581,64 @@ def iq_channelize(x, plan, n0, m0, M, out=None, n_total=None):
     return y
 
 
+def iq_extract(x, n0, n_total, segments, taps, out):
+    """One launch of the extraction kernel (sy11_iq_extract): every segment of ``segments`` — ``sy11.data.extract.SEGMENT`` records
+    (m0, out_off, M, log2d, dphi): the outputs ``[m0, m0 + M)`` on the grid of decimation ``D = 2^log2d`` (output m = capture sample
+    m D), mixed by ``dphi``, low-passed and decimated — is written to ``out[out_off : out_off + M]``.  ``x``, ``n0`` and ``n_total`` as in
+    ``iq_resample``: ``x`` holds the capture's samples ``[n0, n0 + len(x))`` (its base may be an odd sample of a larger tensor) and must
+    cover every segment's support clipped to the capture; samples outside the capture are zeros.  ``taps``: the device buffer of
+    ``sy11.data.extract.taps_on``; ``out``: 1-D contiguous complex64 on x's device.  Each output is, bit for bit, what ``iq_resample``
+    gives with ``plan_resample(fs, fs / D, shift)``.  -> ``out``."""
+    from .data.extract import MAX_LOG2D, SEGMENT, taps_offset
+    _need_gpu(x, taps, out)
+    n0, n_total = int(n0), int(n_total)
+    if x.dtype != torch.complex64 or x.dim() != 1 or not x.is_contiguous() or x.shape[0] == 0:
+        raise _lib.Sy11Error("iq_extract: x must be a non-empty 1-D contiguous complex64 device tensor")
+    n_in = x.shape[0]
+    if n0 < 0 or n0 + n_in > n_total:
+        raise _lib.Sy11Error(f"iq_extract: samples [{n0}, {n0 + n_in}) leave the capture ({n_total} samples)")
+    if out.dtype != torch.complex64 or out.dim() != 1 or not out.is_contiguous() or out.device != x.device or out.shape[0] == 0:
+        raise _lib.Sy11Error("iq_extract: `out` must be a non-empty 1-D contiguous complex64 tensor on x's device")
+    if taps.dtype != torch.float32 or taps.dim() != 1 or not taps.is_contiguous() or taps.device != x.device \
+            or taps.shape[0] != taps_offset(MAX_LOG2D + 1):
+        raise _lib.Sy11Error(f"iq_extract: `taps` must be the {taps_offset(MAX_LOG2D + 1)}-float table of sy11.data.extract.taps_on on x's device")
+    seg = np.ascontiguousarray(segments)
+    if seg.dtype != SEGMENT or seg.ndim != 1 or seg.shape[0] == 0:
+        raise _lib.Sy11Error("iq_extract: `segments` must be a non-empty 1-D array of sy11.data.extract.SEGMENT records")
+    l, M, m0, off = seg["log2d"].astype(np.int64), seg["M"].astype(np.int64), seg["m0"], seg["out_off"]
+    if (l < 0).any() or (l > MAX_LOG2D).any():
+        raise _lib.Sy11Error(f"iq_extract: log2 D must lie in [0, {MAX_LOG2D}]")
+    D = np.int64(1) << l
+    if (M <= 0).any() or (m0 < 0).any() or (m0 >= 2 ** 48).any() or ((m0 + M - 1) * D >= n_total).any():
+        k = int(np.flatnonzero((M <= 0) | (m0 < 0) | (m0 >= 2 ** 48) | ((m0 + M - 1) * D >= n_total))[0])
+        raise _lib.Sy11Error(f"iq_extract: segment {k}: outputs [{int(m0[k])}, {int(m0[k] + M[k])}) at D = {int(D[k])} are not on the capture's "
+                             f"{n_total} samples")
+    if (off < 0).any() or (off + M > out.shape[0]).any():
+        k = int(np.flatnonzero((off < 0) | (off + M > out.shape[0]))[0])
+        raise _lib.Sy11Error(f"iq_extract: segment {k} writes [{int(off[k])}, {int(off[k] + M[k])}) of an output of {out.shape[0]} samples")
+    a = np.where(l == 0, m0, np.maximum((m0 - 16) * D, 0))
+    b = np.where(l == 0, m0 + M, np.minimum((m0 + M + 15) * D + 1, n_total))
+    if (a < n0).any() or (b > n0 + n_in).any():
+        k = int(np.flatnonzero((a < n0) | (b > n0 + n_in))[0])
+        raise _lib.Sy11Error(f"iq_extract: segment {k} reads samples [{int(a[k])}, {int(b[k])}); x holds [{n0}, {n0 + n_in})")
+    lib = _lib.load()
+    tile = np.array([lib.sy11_iq_extract_tile(k) for k in range(MAX_LOG2D + 1)], dtype=np.int64)[l]
+    count = -(-M // tile)                                      # the tile map: one (segment, first output) pair per workgroup
+    n_tile = int(count.sum())
+    if n_in >= 2 ** 31 or out.shape[0] >= 2 ** 31 or n_tile >= 2 ** 31 or seg.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"iq_extract: n_in = {n_in}, len(out) = {out.shape[0]} and the {n_tile} tiles must stay below 2^31 per call")
+    tiles = np.empty((n_tile, 2), dtype=np.int32)
+    tiles[:, 0] = np.repeat(np.arange(seg.shape[0]), count)
+    tiles[:, 1] = (np.arange(n_tile) - np.repeat(np.cumsum(count) - count, count)) * np.repeat(tile, count)
+    table = np.concatenate((seg.view(np.uint8), tiles.reshape(-1).view(np.uint8)))
+    t = torch.from_numpy(table).to(x.device)
+    call("sy11_iq_extract", seg.shape[0], C.c_void_p(table.ctypes.data), C.c_void_p(t.data_ptr()), n_tile,
+         C.c_void_p(table.ctypes.data + seg.nbytes), C.c_void_p(t.data_ptr() + seg.nbytes), _p(taps), n_total, n0, n_in,
+         C.c_void_p(torch.view_as_real(x).data_ptr()), out.shape[0], C.c_void_p(torch.view_as_real(out).data_ptr()), _stream())
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return out
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
