@@ -301,6 +301,19 @@ int sy11_scan_merge(int32_t n, int32_t W, int32_t n_frames, const int32_t* windo
                     const int32_t* cls, const int64_t* start, int32_t metric, float thres, int32_t agnostic, void* workspace,
                     uint8_t* keep, void* stream);
 size_t sy11_scan_merge_workspace_bytes(int32_t n, int32_t W);
+/* Link the boxes of one emission into tracks (no reference counterpart): n rows of rect = [t0_s, f_lo_hz, t1_s, f_hi_hz] f64
+ * (16-byte aligned array, finite, t1 >= t0, f_hi >= f_lo, rows SORTED by t0 ascending) and their classes.  Rows i != j of one class
+ * (agnostic != 0: of any classes) are linked when ov_t >= -gap_t and ov_f >= align * min(bw_i, bw_j), or, with use_f != 0, when
+ * ov_f >= -gap_f and ov_t >= align * min(dur_i, dur_j); ov_t = min(t1) - max(t0), ov_f = min(f_hi) - max(f_lo), dur = t1 - t0,
+ * bw = f_hi - f_lo, all in f64 with no contraction, so a host evaluation decides every pair identically.  label[i] = the smallest
+ * row of i's connected component: unique, whatever the scheduling.  gap_t >= 0, gap_f >= 0 (ignored without use_f), 0 < align <= 1.
+ * Hook-and-compress on the labels with integer atomicMin; pairs are recomputed per pass over the contiguous candidate range of
+ * each row.  workspace: caller-allocated, 16-byte aligned, as many bytes as the ..._workspace_bytes query below returns (O(n): no
+ * pair matrix, no edge list).  *passes (HOST, may be NULL): hook passes run — a few, not O(chain length).  Synchronises the stream
+ * (one host read per two passes).                                                                                              */
+int sy11_scan_link(int32_t n, const double* rect, const int32_t* cls, double gap_t, double gap_f, int32_t use_f, double align,
+                   int32_t agnostic, void* workspace, int32_t* label, int32_t* passes, void* stream);
+size_t sy11_scan_link_workspace_bytes(int32_t n);
 
 /* ---- fused detection criterion (v8DetectionLoss.__call__, utils/loss.py:221-275; TaskAlignedAssigner, utils/tal.py:40-296;
  *      bbox_iou CIoU, utils/metrics.py:171-234).  maps: nl NHWC f32 head maps (B, H_l*W_l, 64+nc); gt: (B, G, 5) rows

@@ -113,6 +113,7 @@ SIGNATURES = {
     "sy11_stft_normalize": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "sy11_stft_windows": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "sy11_scan_merge": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp],
+    "sy11_scan_link": [_i32, _vp, _vp, _f64, _f64, _i32, _f64, _i32, _vp, _vp, _vp, _vp],
     "sy11_image_u8_to_float": [_i32, C.c_int64, _vp, _vp, _vp],
     "sy11_image_resize_bilinear": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "sy11_image_letterbox": [_i32] * 12 + [_vp, _vp, _vp],
@@ -140,6 +141,7 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_nms_workspace_bytes": ([_i32], C.c_size_t),
          "sy11_nms_batched_workspace_bytes": ([_i32, _vp], C.c_size_t),
          "sy11_scan_merge_workspace_bytes": ([_i32, _i32], C.c_size_t),
+         "sy11_scan_link_workspace_bytes": ([_i32], C.c_size_t),
          "sy11_attention_workspace_bytes": ([_i32, _i32, _i32], C.c_size_t),
          "sy11_iq_extract_tile": ([_i32], C.c_int32),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}

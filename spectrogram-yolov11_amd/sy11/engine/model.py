@@ -283,7 +283,7 @@ class YOLO:
 
     def scan(self, source, sample_rate, center_freq=0.0, conf=0.25, iou=0.7, overlap=0.5, batch=64, merge="ios", merge_thres=0.5,
              max_det=300, classes=None, agnostic_nms=False, half=False, stride_frames=None, n_fft=1024, hop=256, imgsz=640,
-             resample_to=None, tune_to=None, channels=None, oversample=2, select=None):
+             resample_to=None, tune_to=None, channels=None, oversample=2, select=None, link=None):
         """Detect over a long IQ capture (no reference counterpart) -> ``ScanResults`` with boxes in strip frames / image rows and
         in seconds / Hz.  ``source``: a 1-D complex64 tensor or ndarray, a ``.npy`` of complex64, or a raw interleaved-float32
         file (``.cf32`` / ``.fc32`` / ``.iq``), opened with ``np.memmap`` and read chunk by chunk.  ``sample_rate`` in Hz,
@@ -295,10 +295,12 @@ class YOLO:
         transform the model knows (``DetectionPredictor.scan``); boxes stay in seconds of the capture and absolute Hz.
         ``channels`` (K, a ``ChannelPlan`` or ``"model"``) / ``oversample`` / ``select``: split a wideband capture into K bands with
         a polyphase filter bank on the GPU and scan every selected band from one read of the capture; the rows carry their band in
-        ``ScanResults.channel`` (``DetectionPredictor.scan``)."""
+        ``ScanResults.channel`` (``DetectionPredictor.scan``).
+        ``link`` = True, or a dict of ``link``'s keywords: link the boxes of one emission into tracks before returning (``link``)."""
         from ..data.spectrogram import SpectrogramProducer, open_iq
-        from .predictor import DetectionPredictor, plan_scan_ddc
+        from .predictor import DetectionPredictor, link_keywords, plan_scan_ddc
         trained = (self.ckpt or {}).get("train_args") or {}
+        link = link_keywords(link)                            # argument errors come first, before anything touches the device
         if channels is not None:                              # argument errors come first, before anything touches the device
             from ..data.channelize import plan_scan_channels
             channels, select = plan_scan_channels(sample_rate, channels, oversample, select, trained, resample_to, tune_to)
@@ -318,7 +320,17 @@ class YOLO:
         self._scanner.trained = trained
         return self._scanner.scan(open_iq(source), sample_rate, center_freq=center_freq, overlap=overlap, batch=batch, merge=merge,
                                   merge_thres=merge_thres, stride_frames=stride_frames, resample_to=resample_to, tune_to=tune_to,
-                                  channels=channels, oversample=oversample, select=select)
+                                  channels=channels, oversample=oversample, select=select, link=link)
+
+    def link(self, results, gap_t="auto", gap_f="auto", align=0.5, agnostic=False, hop=None):
+        """Link the boxes of one emission longer than a window, or wider than a band, into tracks -> the same ``results`` with
+        ``results.track`` (the track of every row) and ``results.tracks`` (``sy11.data.link.Tracks``: one union rectangle, class and
+        confidence per emission) set; ``extract(source, results.tracks, ...)`` then cuts one clip per emission
+        (``DetectionPredictor.link``)."""
+        from ..data.link import link_results
+        tracks = link_results(results, self.device, gap_t, gap_f, align, agnostic, hop)
+        results.track, results.tracks = tracks.track, tracks
+        return results
 
     def extract(self, source, results, sample_rate, center_freq=0.0, rows=None, pad_t=0.0, pad_f=0.1, decimate="auto", chunk_samples=1 << 24):
         """Take every detection of ``results`` (what ``scan`` returned for this capture) out of the recording as baseband IQ ->

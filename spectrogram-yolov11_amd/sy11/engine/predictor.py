@@ -63,13 +63,17 @@ class ScanResults:
     absolute Hz, and ``resample`` is the plan that was used.  After a channelised scan ``channel`` (n,) int64 is the band every
     row was found in and ``channelizer`` the ``ChannelPlan``: ``sample_rate`` is the bands' rate (frames, ``boxes`` and ``start`` count
     a band's samples; all bands share ``start``), ``center_freq`` stays the capture's (band k is centred at ``center_freq +
-    channelizer.offset_hz[k]``), ``tf`` is in seconds of the capture and absolute Hz; rows are ordered by channel."""
+    channelizer.offset_hz[k]``), ``tf`` is in seconds of the capture and absolute Hz; rows are ordered by channel.
+    ``hop`` is the STFT hop of the scan (None on a hand-built result).  ``track`` (n,) int64 — the track of every row — and
+    ``tracks`` (``sy11.data.link.Tracks``) are set by ``link`` / ``scan(link=...)`` and None on every other result."""
 
     def __init__(self, boxes, window, tf, names, start, sample_rate, center_freq, resample=None, channel=None, channelizer=None):
         self.boxes, self.window, self.tf, self.names = boxes, window, tf, names
         self.start, self.sample_rate, self.center_freq = start, sample_rate, center_freq
         self.resample = resample                            # the ResamplePlan of a resampled / retuned scan, else None
         self.channel, self.channelizer = channel, channelizer       # a channelised scan's band per row and its ChannelPlan, else None
+        self.hop = None                                     # the scan's STFT hop: what gap_t="auto" of link counts in
+        self.track, self.tracks = None, None                # set by link: the track of every row and the Tracks table
 
     def __len__(self):
         return self.boxes.shape[0]
@@ -152,7 +156,7 @@ class DetectionPredictor:
 
     @torch.no_grad()
     def scan(self, iq, sample_rate, center_freq=0.0, overlap=0.5, batch=64, merge="ios", merge_thres=0.5, stride_frames=None,
-             start=None, resample_to=None, tune_to=None, channels=None, oversample=2, select=None):
+             start=None, resample_to=None, tune_to=None, channels=None, oversample=2, select=None, link=None):
         """Run the model over a capture of any length -> ``ScanResults``.  ``iq``: what ``sy11.data.spectrogram.open_iq`` returns
         (1-D complex64 samples: array, tensor or ``np.memmap``).  Windows come from ``plan_windows(len(iq), overlap | stride_frames)``
         (or ``start``); per chunk of ``batch`` windows: the producer's strip images -> ``inference`` (graph replay for full chunks,
@@ -174,17 +178,23 @@ class DetectionPredictor:
         their width, so an emission cut by one band's edge is whole in the next; ``select`` = the bands to scan (default: all but
         K/2, which wraps round the capture's edge).  Per chunk there is ONE channelise launch, then the usual steps per band; after
         the per-band seam merges a cross-band merge (``channelize.merge_channels``, in seconds / Hz) runs when ``oversample`` is 2
-        and ``merge`` is not None.  ``channels`` excludes ``resample_to`` / ``tune_to``."""
+        and ``merge`` is not None.  ``channels`` excludes ``resample_to`` / ``tune_to``.
+
+        ``link`` = True, or a dict of ``link``'s keywords, runs ``link`` on the result before it is returned (``results.track`` /
+        ``results.tracks``); None changes nothing."""
         from .. import ops as kops
         from ..data import spectrogram as sp
         if self.producer is None:
             raise ValueError("scan needs a SpectrogramProducer")
         if merge not in (None, "ios", "iou"):
             raise ValueError(f"merge must be 'ios', 'iou' or None, got {merge!r}")
+        link = link_keywords(link)
         p = self.producer
         if channels is not None:
-            return self._scan_channels(iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start,
-                                       resample_to, tune_to, channels, oversample, select)
+            res = self._scan_channels(iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start,
+                                      resample_to, tune_to, channels, oversample, select)
+            res.hop = p.hop
+            return res if link is None else self.link(res, **link)
         plan = None
         if resample_to is not None or tune_to is not None:
             from ..data.resample import ResampledCapture, ResamplePlan
@@ -223,7 +233,24 @@ class DetectionPredictor:
         boxes[:, 0] += off
         boxes[:, 2] += off
         tf = scan_boxes_to_tf(boxes, sample_rate, center_freq, p)
-        return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq), plan)
+        res = ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(sample_rate), float(center_freq), plan)
+        res.hop = p.hop
+        return res if link is None else self.link(res, **link)
+
+    def link(self, results, gap_t="auto", gap_f="auto", align=0.5, agnostic=False, hop=None):
+        """Link the boxes of one emission — the pieces that windows shorter than it, or bands narrower than it, cut it into —
+        into tracks (``sy11.data.link``, ``csrc/link.hip``) -> the same ``results``, with ``results.track`` (n,) int64 the track of
+        every row and ``results.tracks`` the ``Tracks`` table (union rectangle, best class, confidence, member rows), which
+        ``extract`` takes in place of the results to cut one clip per emission.  Rows of one class (``agnostic``: of any) are linked
+        when they continue each other in time — at most ``gap_t`` seconds apart ("auto": 8 STFT hops of the scanned rate) and
+        sharing ``align`` of the narrower one's bandwidth — or, with ``gap_f`` (Hz; "auto": 0.0 behind a filter bank with
+        ``oversample`` 2, else None = off), in frequency; a track is a connected component.  The defaults are judgements, not
+        measurements.  Argument errors are ``ValueError``s raised before anything touches the device; an empty ``results`` gives an
+        empty ``Tracks`` with no launch."""
+        from ..data.link import link_results
+        tracks = link_results(results, self.device, gap_t, gap_f, align, agnostic, hop)
+        results.track, results.tracks = tracks.track, tracks
+        return results
 
     def extract(self, iq, results, sample_rate, center_freq=0.0, rows=None, pad_t=0.0, pad_f=0.1, decimate="auto", chunk_samples=1 << 24):
         """Every detection of ``results`` (a ``ScanResults`` of this capture) as baseband IQ -> ``sy11.data.extract.Extraction``: per row
@@ -303,6 +330,21 @@ class DetectionPredictor:
                                                    a["agnostic_nms"]))
             boxes, wins, chan, tf = boxes[keep], wins[keep], chan[keep], tf[keep]
         return ScanResults(boxes, wins, tf, getattr(self.model, "names", None), start, float(fs_out), float(center_freq), None, chan, plan)
+
+
+def link_keywords(link):
+    """``scan(link=...)`` -> the keywords of ``link`` or None; their argument errors are raised here, before the scan starts."""
+    if link is None or link is False:
+        return None
+    if link is not True and not isinstance(link, dict):
+        raise ValueError(f"link must be None, True or a dict of link's keywords, got {link!r}")
+    from ..data.link import check_link_args
+    kw = {} if link is True else dict(link)
+    unknown = set(kw) - {"gap_t", "gap_f", "align", "agnostic", "hop"}
+    if unknown:
+        raise ValueError(f"link: unknown keywords {sorted(unknown)}")
+    check_link_args(**kw)
+    return kw
 
 
 def plan_scan_ddc(sample_rate, center_freq, resample_to=None, tune_to=None, trained=None):

@@ -7,6 +7,7 @@ An NHWC *view* is a torch tensor of shape (B, H, W, C) whose strides are (H*W*ld
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -668,6 +669,43 @@ def scan_merge(window, boxes, score, cls, start, n_frames, metric="ios", thres=0
          _p(cls.to(torch.int32).contiguous()), _p(start.to(dev).contiguous()), SCAN_METRICS[metric], float(thres), 1 if agnostic else 0,
          _p(ws), _p(keep), _stream())
     return keep.bool()
+
+
+def scan_link(tf, cls, gap_t, gap_f=None, align=0.5, agnostic=False, return_passes=False):
+    """Tracks of a scan's rows: ``tf`` (n, 4) float64 [t0_s, f_lo_hz, t1_s, f_hi_hz] and ``cls`` (n,) integer on the device -> (n,) int64
+    labels in the caller's row order, label[i] = the smallest row index of the connected component of row i under the link relation
+    of include/sy11.h (``gap_f`` None: the time branch alone).  One stable sort by t0, one call, one un-permute, all on the device.
+    ``return_passes``: also the number of hook passes the call ran."""
+    _need_gpu(tf, cls)
+    n = tf.shape[0]
+    if tf.dim() != 2 or tf.shape[1] != 4 or tf.dtype != torch.float64 or cls.shape != (n,) or cls.dtype.is_floating_point \
+            or cls.dtype == torch.bool or cls.device != tf.device:
+        raise _lib.Sy11Error("scan_link: expected tf (n, 4) float64 and cls (n,) of an integer type on tf's device")
+    use_f = gap_f is not None
+    gap_t, gap_f, align = float(gap_t), float(gap_f) if use_f else 0.0, float(align)
+    if not (math.isfinite(gap_t) and gap_t >= 0 and math.isfinite(gap_f) and gap_f >= 0 and 0 < align <= 1):
+        raise _lib.Sy11Error(f"scan_link: gap_t and gap_f must be finite and >= 0 and align in (0, 1], got {gap_t!r} / {gap_f!r} / {align!r}")
+    if n >= 2 ** 31:
+        raise _lib.Sy11Error(f"scan_link: {n} rows; one call takes fewer than 2^31")
+    if n == 0:
+        out = torch.zeros((0,), dtype=torch.int64, device=tf.device)
+        return (out, 0) if return_passes else out
+    if not bool(torch.isfinite(tf).all()):
+        raise _lib.Sy11Error("scan_link: every value of tf must be finite")
+    if bool(((tf[:, 2] < tf[:, 0]) | (tf[:, 3] < tf[:, 1])).any()):
+        raise _lib.Sy11Error("scan_link: a rectangle is inverted (t1 < t0 or f_hi < f_lo)")
+    _, order = torch.sort(tf[:, 0], stable=True)               # order[k] = the caller's row at sorted position k
+    rect = tf[order].contiguous()
+    label = torch.empty((n,), dtype=torch.int32, device=tf.device)
+    ws = torch.empty((_lib.load().sy11_scan_link_workspace_bytes(n),), dtype=torch.uint8, device=tf.device)
+    passes = C.c_int32(0)
+    call("sy11_scan_link", n, _p(rect), _p(cls[order].to(torch.int32).contiguous()), gap_t, gap_f, int(use_f), align, int(bool(agnostic)),
+         _p(ws), _p(label), C.byref(passes), _stream())
+    root = label.to(torch.int64)                               # the component of sorted position k, named by a sorted position
+    first = torch.full((n,), n, dtype=torch.int64, device=tf.device).scatter_reduce(0, root, order, "amin")   # its smallest caller row
+    out = torch.empty((n,), dtype=torch.int64, device=tf.device)
+    out[order] = first[root]
+    return (out, int(passes.value)) if return_passes else out
 
 
 # ------------------------------------------------------------------------------------------------ image side of preprocess
