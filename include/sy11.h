@@ -531,6 +531,61 @@ int sy11_iq_extract(int32_t n_seg, const sy11_iq_segment* seg_host, const sy11_i
                     const int32_t* tile_host, const int32_t* tile, const float* taps, int64_t n_total, int64_t n0, int32_t n_in,
                     const float* in, int64_t out_len, float* out, void* stream);
 
+/* ---- measurement: Welch power spectrum, noise, bandwidth and centroid of every detection of a scan (spec in DESIGN.md §4) ----
+ * N = n_fft in {64 128 256 512 1024}, H = N / 2.  Frame j is the capture's samples [j H  j H + N), anchored at sample 0;
+ *   X_j[k] = sum_{i < N} window[i] x[j H + i] e^{-2 pi i k i / N}     k = 0 .. N - 1 (bin k >= N / 2 is the signed bin k - N)
+ * Frames are grouped on their absolute index, G = the value of sy11_iq_psd_group frames per group.
+ *
+ * Stage 1, sy11_iq_psd.  An item is the frames [j0  j0 + nf) of one box, all of ONE group (1 <= nf <= G).  Per item
+ *   partial[row N + k]     = f32(sum_j |X_j[k]|^2)                          frames ascending, one after the other
+ *   env[env_off + (j - j0)] = f32((sum_{k_lo <= k <= k_hi} |X_j[k]|^2) / nw2)   signed bins; only when env != NULL
+ * computed in float64 (the product window[i] x is exact there) and rounded once, to the f32 that is stored.
+ * window: DEVICE N f32; twiddle: DEVICE N / 2 complex128, e^{-2 pi i m / N}, 16-byte aligned; nw2 = N sum window^2 in float64.  item: DEVICE n_item
+ * items; item_host: a HOST copy, checked entry by entry before anything is launched: no item may read samples outside in[] -
+ * [j0 H  (j0 + nf - 1) H + N), which must also lie on the capture [0  n_total) - or write outside partial[0  n_rows N) or
+ * env[0  env_len), every row is written by one item of the call, and -N/2 <= k_lo <= k_hi < N/2.  in: complex64 samples
+ * n0 <= i < n0 + n_in (absolute indices of the capture; in may start at an odd sample of its allocation).  The FFT runs in one fixed
+ * order (radix-2 decimation in frequency) and so does every sum, so a value depends on (box  frames  capture) only, never on the
+ * launch shape, the item's place in the table or on how the caller cut the capture into calls.  No atomics.
+ * Nothing is launched on an error.
+ *
+ * Stage 2, sy11_psd_measure: one launch after the last stage-1 call, float64 throughout, every product and sum rounded on its own.
+ * Per box, with the rows row0 .. row0 + n_rows - 1 of partial (its groups, ascending):
+ *   P[k]         = (sum over the rows of partial[row N + (k mod N)], ascending, one after the other) scale      -N/2 <= k < N/2
+ *   noise_median = the median (mean of the two middle values for an even count) of P over the noise bins: -noise_l <= k <= noise_l - 1
+ *                  and k outside [s_lo  s_hi];   NaN when there are none;    nd = noise_median corr
+ *   p_in         = sum of P[k], k_lo <= k <= k_hi, ascending
+ *   c[k]         = max(P[k] - nd  0), or P[k] when there are no noise bins;   sum_c = sum of c[k], sum_kc = sum of k c[k] over
+ *                  s_lo <= k <= s_hi, ascending
+ *   k_dn, k_up   = the first k at which the running sum of c reaches frac_lo sum_c and frac_hi sum_c
+ * psd: n_box N float64, psd[b N + k + N/2] = P[k]; out_f: n_box 4 float64 (p_in  noise_median  sum_c  sum_kc); out_i: n_box 4 int32
+ * (k_dn  k_up  n_in  n_noise).  box: DEVICE table, box_host: its HOST copy, checked before the launch (rows inside partial[0  n_rows N),
+ * -N/2 <= s_lo <= k_lo <= k_hi <= s_hi < N/2, 0 <= noise_l <= N/2, scale and corr positive and finite).
+ * Nothing is launched on an error.                                                                                      */
+typedef struct sy11_psd_item {
+  int64_t j0;                  /* first frame (absolute index: capture sample j0 H)                                */
+  int64_t env_off;             /* first f32 of the item's frames in env (ignored when env is NULL)                 */
+  int32_t nf;                  /* number of frames, 1 .. G, all with the same j / G                                */
+  int32_t row;                 /* row of the partial table the item writes                                         */
+  int32_t k_lo, k_hi;          /* the box's signed bins, for the envelope                                          */
+} sy11_psd_item;
+typedef struct sy11_psd_box {
+  int64_t row0;                /* first row of the box in the partial table                                        */
+  int32_t n_rows;              /* its number of rows (groups)                                                      */
+  int32_t k_lo, k_hi;          /* in-box bins (signed)                                                             */
+  int32_t s_lo, s_hi;          /* search span                                                                      */
+  int32_t noise_l;             /* noise bins lie in [-noise_l  noise_l - 1]                                        */
+  double scale;                /* 1 / (J N W2)                                                                     */
+  double corr;                 /* median-to-mean correction, 1 / (1 - 1 / (9 J))^3                                 */
+} sy11_psd_box;
+int32_t sy11_iq_psd_group(void);                  /* G: frames per group, a constant of the build */
+int sy11_iq_psd(int32_t n_fft, int32_t n_item, const sy11_psd_item* item_host, const sy11_psd_item* item, const float* window,
+                const double* twiddle, double nw2, int64_t n_total, int64_t n0, int32_t n_in, const float* in, int64_t n_rows,
+                float* partial, int64_t env_len, float* env, void* stream);
+int sy11_psd_measure(int32_t n_fft, int32_t n_box, const sy11_psd_box* box_host, const sy11_psd_box* box, double frac_lo,
+                     double frac_hi, int64_t n_rows, const float* partial, double* psd, double* out_f, int32_t* out_i,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

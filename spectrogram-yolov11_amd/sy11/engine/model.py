@@ -340,6 +340,18 @@ class YOLO:
         from ..data.spectrogram import open_iq
         return extract_results(open_iq(source), results, sample_rate, center_freq, self.device, rows, pad_t, pad_f, decimate, chunk_samples)
 
+    def measure(self, source, results, sample_rate, center_freq=0.0, rows=None, n_fft=1024, pad_f=0.25, beta=0.99, noise_band=0.8,
+                envelope=True, chunk_samples=1 << 24):
+        """Measure every detection of ``results`` (what ``scan`` returned for this capture, or its ``tracks``) on the GPU ->
+        ``sy11.data.measure.Measurement``: received power, noise density, SNR, the ``beta`` occupied bandwidth, a power-weighted centre
+        frequency, the Welch spectrum and, with ``envelope``, the in-box power of every frame (``DetectionPredictor.measure``).
+        ``source``, ``results``, ``rows``, ``sample_rate`` and ``center_freq`` as in ``extract``: the rate and centre are the capture's own, also
+        after ``scan(resample_to=)`` or ``scan(channels=)``."""
+        from ..data.measure import measure_results
+        from ..data.spectrogram import open_iq
+        return measure_results(open_iq(source), results, sample_rate, center_freq, self.device, rows, n_fft, pad_f, beta, noise_band,
+                               envelope, chunk_samples)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

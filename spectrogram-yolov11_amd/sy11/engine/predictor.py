@@ -265,6 +265,20 @@ class DetectionPredictor:
         from ..data.extract import extract_results
         return extract_results(iq, results, sample_rate, center_freq, self.device, rows, pad_t, pad_f, decimate, chunk_samples)
 
+    def measure(self, iq, results, sample_rate, center_freq=0.0, rows=None, n_fft=1024, pad_f=0.25, beta=0.99, noise_band=0.8,
+                envelope=True, chunk_samples=1 << 24):
+        """Measure every detection of ``results`` (a ``ScanResults`` of this capture, or its ``Tracks``) -> ``sy11.data.measure.Measurement``:
+        the Welch power spectrum of the box's time span (periodic Hann, ``n_fft`` in {64 .. 1024}, half-overlapped frames anchored at
+        sample 0), all boxes of a staged chunk in ONE launch and one reduction launch at the end (``csrc/measure.hip``).  From it: the
+        power inside the box's bins, the noise density (the median of the bins outside the box widened by ``pad_f`` on both sides, within
+        the central ``noise_band`` of the capture, corrected to a mean), the SNR, the ``beta`` occupied bandwidth and the power-weighted
+        centre over the widened span, and with ``envelope`` the in-box power of every frame.  ``iq``, ``sample_rate`` / ``center_freq`` and
+        ``rows`` as in ``extract``.  Argument errors are ``ValueError``s raised before anything touches the device; an empty ``results``
+        gives an empty ``Measurement`` with no launch."""
+        from ..data.measure import measure_results
+        return measure_results(iq, results, sample_rate, center_freq, self.device, rows, n_fft, pad_f, beta, noise_band, envelope,
+                               chunk_samples)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

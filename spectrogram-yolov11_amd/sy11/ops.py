@@ -640,6 +640,107 @@ def iq_extract(x, n0, n_total, segments, taps, out):
     return out
 
 
+def iq_psd(x, n0, n_total, n_fft, items, window, twiddle, nw2, partial, env=None):
+    """One launch of the Welch kernel (sy11_iq_psd): every item of ``items`` — ``sy11.data.measure.ITEM`` records (j0, env_off, nf, row,
+    k_lo, k_hi): the frames ``[j0, j0 + nf)`` of one box, all of one group of ``sy11_iq_psd_group()`` frames — writes the sum of its
+    frames' ``|X_j[k]|^2`` to row ``row`` of ``partial`` (rows, n_fft) f32 and, with ``env`` (1-D f32), the in-box power of each frame to
+    ``env[env_off + (j - j0)]``.  ``x``, ``n0`` and ``n_total`` as in ``iq_extract``; frame j is the capture's samples
+    ``[j n_fft / 2, j n_fft / 2 + n_fft)``.  ``window`` (n_fft,) f32, ``twiddle`` (n_fft / 2,) complex128 and ``nw2`` come from
+    ``sy11.data.measure.tables_on``.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``partial``."""
+    from .data.measure import ITEM, N_FFT
+    _need_gpu(x, window, twiddle, partial, env)
+    n0, n_total, n_fft = int(n0), int(n_total), int(n_fft)
+    if n_fft not in N_FFT:
+        raise _lib.Sy11Error(f"iq_psd: n_fft must be one of {N_FFT}, got {n_fft}")
+    if x.dtype != torch.complex64 or x.dim() != 1 or not x.is_contiguous() or x.shape[0] == 0:
+        raise _lib.Sy11Error("iq_psd: x must be a non-empty 1-D contiguous complex64 device tensor")
+    n_in = x.shape[0]
+    if n0 < 0 or n0 + n_in > n_total:
+        raise _lib.Sy11Error(f"iq_psd: samples [{n0}, {n0 + n_in}) leave the capture ({n_total} samples)")
+    if partial.dtype != torch.float32 or partial.dim() != 2 or partial.shape[1] != n_fft or partial.shape[0] == 0 or not partial.is_contiguous() \
+            or partial.device != x.device:
+        raise _lib.Sy11Error(f"iq_psd: `partial` must be a non-empty contiguous (rows, {n_fft}) float32 tensor on x's device")
+    if env is not None and (env.dtype != torch.float32 or env.dim() != 1 or env.shape[0] == 0 or not env.is_contiguous() or env.device != x.device):
+        raise _lib.Sy11Error("iq_psd: `env` must be None or a non-empty 1-D contiguous float32 tensor on x's device")
+    if window.dtype != torch.float32 or window.shape != (n_fft,) or not window.is_contiguous() or window.device != x.device \
+            or twiddle.dtype != torch.complex128 or twiddle.shape != (n_fft // 2,) or not twiddle.is_contiguous() or twiddle.device != x.device:
+        raise _lib.Sy11Error(f"iq_psd: `window` / `twiddle` must be the ({n_fft},) float32 and ({n_fft // 2},) complex128 tables on x's device")
+    it = np.ascontiguousarray(items)
+    if it.dtype != ITEM or it.ndim != 1 or it.shape[0] == 0:
+        raise _lib.Sy11Error("iq_psd: `items` must be a non-empty 1-D array of sy11.data.measure.ITEM records")
+    G, H = _lib.load().sy11_iq_psd_group(), n_fft // 2
+    j0, nf, row = it["j0"], it["nf"].astype(np.int64), it["row"].astype(np.int64)
+    bad = (nf < 1) | (nf > G) | (j0 < 0) | (j0 >= 2 ** 48) | (j0 // G != (j0 + nf - 1) // G)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_psd: item {k}: frames [{int(j0[k])}, {int(j0[k] + nf[k])}) are not 1 .. {G} frames of one group")
+    a, b = j0 * H, (j0 + nf - 1) * H + n_fft
+    bad = (a < n0) | (b > n0 + n_in)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_psd: item {k} reads samples [{int(a[k])}, {int(b[k])}); x holds [{n0}, {n0 + n_in})")
+    bad = (row < 0) | (row >= partial.shape[0])
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        k = int(np.flatnonzero(bad)[0]) if bad.any() else int(np.flatnonzero(np.bincount(row)[row] > 1)[0])
+        raise _lib.Sy11Error(f"iq_psd: item {k} writes row {int(row[k])} of a partial table of {partial.shape[0]} rows (a row takes one item)")
+    bad = (it["k_lo"] < -H) | (it["k_lo"] > it["k_hi"]) | (it["k_hi"] >= H)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_psd: item {k}: bins [{int(it['k_lo'][k])}, {int(it['k_hi'][k])}] are not in [{-H}, {H})")
+    if env is not None:
+        bad = (it["env_off"] < 0) | (it["env_off"] + nf > env.shape[0])
+        if bad.any():
+            k = int(np.flatnonzero(bad)[0])
+            raise _lib.Sy11Error(f"iq_psd: item {k} writes [{int(it['env_off'][k])}, {int(it['env_off'][k] + nf[k])}) of an envelope of "
+                                 f"{env.shape[0]} values")
+    if n_in >= 2 ** 31 or it.shape[0] >= 2 ** 31 or partial.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"iq_psd: n_in = {n_in}, the {it.shape[0]} items and the {partial.shape[0]} rows must stay below 2^31 per call")
+    t = torch.from_numpy(it.view(np.uint8)).to(x.device)
+    call("sy11_iq_psd", n_fft, it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), _p(window),
+         C.c_void_p(torch.view_as_real(twiddle).data_ptr()), float(nw2), n_total, n0, n_in, C.c_void_p(torch.view_as_real(x).data_ptr()),
+         partial.shape[0], _p(partial), 0 if env is None else env.shape[0], _p(env), _stream())
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return partial
+
+
+def psd_measure(partial, boxes, frac_lo, frac_hi):
+    """The reduction of a measurement (sy11_psd_measure), one launch: ``partial`` (rows, n_fft) f32 as ``iq_psd`` filled it, ``boxes`` —
+    ``sy11.data.measure.BOX`` records (row0, n_rows, k_lo, k_hi, s_lo, s_hi, noise_l, scale, corr) -> ``(psd, out_f, out_i)``: (k, n_fft)
+    float64 in signed-bin order, (k, 4) float64 [p_in, noise_median, sum_c, sum_kc] and (k, 4) int32 [k_dn, k_up, n_in, n_noise], on the
+    device; float64 throughout, in the orders of include/sy11.h.  A refused call raises ``Sy11Error`` and writes nothing."""
+    from .data.measure import BOX, N_FFT
+    _need_gpu(partial)
+    if partial.dtype != torch.float32 or partial.dim() != 2 or partial.shape[1] not in N_FFT or partial.shape[0] == 0 or not partial.is_contiguous():
+        raise _lib.Sy11Error(f"psd_measure: `partial` must be a non-empty contiguous (rows, n_fft) float32 device tensor, n_fft one of {N_FFT}")
+    n_fft, H = partial.shape[1], partial.shape[1] // 2
+    bx = np.ascontiguousarray(boxes)
+    if bx.dtype != BOX or bx.ndim != 1 or bx.shape[0] == 0 or bx.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error("psd_measure: `boxes` must be a non-empty 1-D array of sy11.data.measure.BOX records")
+    frac_lo, frac_hi = float(frac_lo), float(frac_hi)
+    if not 0.0 <= frac_lo <= frac_hi <= 1.0:
+        raise _lib.Sy11Error(f"psd_measure: need 0 <= frac_lo <= frac_hi <= 1, got {frac_lo!r} / {frac_hi!r}")
+    bad = (bx["n_rows"] < 1) | (bx["row0"] < 0) | (bx["row0"] + bx["n_rows"] > partial.shape[0])
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"psd_measure: box {k} sums rows [{int(bx['row0'][k])}, {int(bx['row0'][k]) + int(bx['n_rows'][k])}) of a partial table "
+                             f"of {partial.shape[0]} rows")
+    bad = (bx["s_lo"] < -H) | (bx["s_lo"] > bx["k_lo"]) | (bx["k_lo"] > bx["k_hi"]) | (bx["k_hi"] > bx["s_hi"]) | (bx["s_hi"] >= H) \
+        | (bx["noise_l"] < 0) | (bx["noise_l"] > H)
+    if bad.any():
+        raise _lib.Sy11Error(f"psd_measure: box {int(np.flatnonzero(bad)[0])}: need -N/2 <= s_lo <= k_lo <= k_hi <= s_hi < N/2 and 0 <= noise_l <= N/2")
+    if not (np.isfinite(bx["scale"]).all() and np.isfinite(bx["corr"]).all() and (bx["scale"] > 0).all() and (bx["corr"] > 0).all()):
+        raise _lib.Sy11Error("psd_measure: scale and corr must be positive and finite")
+    dev, k = partial.device, bx.shape[0]
+    psd = torch.empty((k, n_fft), dtype=torch.float64, device=dev)
+    out_f = torch.empty((k, 4), dtype=torch.float64, device=dev)
+    out_i = torch.empty((k, 4), dtype=torch.int32, device=dev)
+    t = torch.from_numpy(bx.view(np.uint8)).to(dev)
+    call("sy11_psd_measure", n_fft, k, C.c_void_p(bx.ctypes.data), C.c_void_p(t.data_ptr()), frac_lo, frac_hi, partial.shape[0], _p(partial),
+         _p(psd), _p(out_f), _p(out_i), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return psd, out_f, out_i
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
