@@ -586,6 +586,55 @@ int sy11_psd_measure(int32_t n_fft, int32_t n_box, const sy11_psd_box* box_host,
                      double frac_hi, int64_t n_rows, const float* partial, double* psd, double* out_f, int32_t* out_i,
                      void* stream);
 
+/* ---- characterisation: symbol rate, carrier offset and kurtosis of every clip of an extraction (spec in DESIGN.md §4) ----
+ * N = n_fft in {64 128 256 512 1024}, H = N / 2.  A clip is len complex64 samples at in[off]; its frame j is the clip's samples
+ * [j H  j H + N), j = 0 .. J - 1, J = (len - N) / H + 1.  With x a sample, y_0 = |x|^2, y_1 = x^2, y_2 = x^4 (formed in float64) and
+ *   Y_q,j[k] = sum_{i < N} window[i] y_q[j H + i] e^{-2 pi i k i / N}     k = 0 .. N - 1 (bin k >= N / 2 is the signed bin k - N)
+ * Frames are grouped on their index in the clip, G = the value of sy11_iq_cyclo_group frames per group.
+ *
+ * Stage 1, sy11_iq_cyclo.  An item is the frames [j0  j0 + nf) of one clip, all of ONE group (1 <= nf <= G).  Per item
+ *   partial[(row 3 + q) N + k] = f32(sum_j |Y_q,j[k]|^2)                    frames ascending, one after the other;  q = 0, 1, 2
+ *   mom[row 4 + 0 .. 3]        = sum of Re x^2, Im x^2, |x|^2, |x|^4 over the clip's samples [j0 H  (j0 + nf) H), and with last = 1
+ *                                over [j0 H  (j0 + nf - 1) H + N): the items of a clip count every sample of its frames once
+ * computed in float64; a partial value is rounded once, to the f32 that is stored.  window, twiddle: the tables of sy11_iq_psd.  item: DEVICE
+ * n_item items; item_host: a HOST copy, checked entry by entry before anything is launched: the clip lies inside in[0  n_in) and holds a
+ * frame, the item's frames are frames of the clip and of one group, last = 1 exactly on the item that ends the clip, and every row of
+ * partial[0  n_rows 3 N) / mom[0  n_rows 4) is written by one item of the call.  in: the packed complex64 clips (a clip may start
+ * at an odd sample).  One fixed order for the FFT and for every sum: a value depends on (clip  frames) only.  No atomics.
+ * Nothing is launched on an error.
+ *
+ * Stage 2, sy11_cyclo_peaks: one launch, one workgroup per (clip, q), float64 throughout, every product and sum rounded on its own.
+ * With the rows row0 .. row0 + n_rows - 1 of partial (the clip's groups, ascending):
+ *   P_q[k]  = (sum over the rows of partial[(row 3 + q) N + (k mod N)], ascending, one after the other) scale      -N/2 <= k < N/2
+ *   search  = k_min <= k <= N/2 - 1 for q = 0 (the spectrum of a real sequence is symmetric; DC and the window's main lobe stay out),
+ *             every k for q = 1, 2;   peak = the first maximum of P_q over it in ascending k;   median over it as in sy11_psd_measure
+ * spectra: n_clip 3 N float64, spectra[(clip 3 + q) N + k + N/2] = P_q[k].  out: n_clip 22 float64 per clip: at 4 q: P_q[peak]  P_q[peak - 1]
+ * P_q[peak + 1] (cyclic)  median;  12 .. 15: the clip's moments (Re m20  Im m20  m21  m42), its rows of mom added ascending;  16 + 2 q: peak,
+ * 17 + 2 q: the size of the search set (integers, exact in float64).  row: DEVICE table, row_host: its HOST copy, checked before the
+ * launch (rows inside partial, clip < n_clip and written once, 1 <= k_min <= N/2 - 1, scale positive and finite).  Entries of spectra
+ * and out of clips that no row names are left alone.  Nothing is launched on an error.                                        */
+typedef struct sy11_cyclo_item {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip, >= N                                                        */
+  int32_t j0;                  /* first frame of the item (index in the clip)                                      */
+  int32_t nf;                  /* number of frames, 1 .. G, all with the same j / G                                */
+  int32_t row;                 /* row of the partial and moment tables the item writes                             */
+  int32_t last;                /* 1: the item ends the clip and owns the last frame's second half; else 0          */
+} sy11_cyclo_item;
+typedef struct sy11_cyclo_row {
+  int64_t row0;                /* first row of the clip in the partial table                                       */
+  int32_t n_rows;              /* its number of rows (groups)                                                      */
+  int32_t clip;                /* the row of spectra / out it writes                                               */
+  int32_t k_min;               /* q = 0 searches [k_min  N/2 - 1]                                                  */
+  int32_t reserved;            /* 0                                                                                */
+  double scale;                /* 1 / (J N W2)                                                                     */
+} sy11_cyclo_row;
+int32_t sy11_iq_cyclo_group(void);                /* G: frames per group, a constant of the build */
+int sy11_iq_cyclo(int32_t n_fft, int32_t n_item, const sy11_cyclo_item* item_host, const sy11_cyclo_item* item, const float* window,
+                  const double* twiddle, int64_t n_in, const float* in, int64_t n_rows, float* partial, double* mom, void* stream);
+int sy11_cyclo_peaks(int32_t n_fft, int32_t n_row, const sy11_cyclo_row* row_host, const sy11_cyclo_row* row, int64_t n_rows,
+                     const float* partial, const double* mom, int32_t n_clip, double* spectra, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 //    slot, then a xor butterfly over the 64 lanes.  Nothing depends on the item's place in the launch or on the chunk.
 //  * Stage 2 is tiny: a bitonic sort of at most 1024 doubles in LDS for the median, the ordered sums by one thread.
 #include "common.h"
+#include "fft_lds.h"
 
 #include <math.h>
 
@@ -28,12 +29,10 @@
 
 namespace {
 
-constexpr int PSD_GROUP = 16;                  // frames per group: at N = 64 one pass of the 1024-slot image is one group
-constexpr int PSD_SLOTS = 1024;
+using namespace sy11_fft;                      // the FFT rounds and the bitonic sort, shared with cyclo.hip
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 w) { return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+constexpr int PSD_GROUP = 16;                  // frames per group: at N = 64 one pass of the 1024-slot image is one group
+constexpr int PSD_SLOTS = FFT_SLOTS;
 
 template <int L>
 __global__ __launch_bounds__(256) void psd_kernel(const sy11_psd_item* __restrict__ items, const float* __restrict__ window,
@@ -53,49 +52,21 @@ __global__ __launch_bounds__(256) void psd_kernel(const sy11_psd_item* __restric
   for (int f0 = 0; f0 < it.nf; f0 += F) {
     const int nfp = min(F, it.nf - f0);                                   // frames of this pass
     double2 e[4];
+    {                                                                     // the first round's input: from global memory, windowed
+      constexpr int h2 = N / 4;
+      const int base = fft_first_slot<L>(t), f = base >> L, p = base & (N - 1);
+      const float2* src = in + ((it.j0 + f0 + f) * H + p - n0);
 #pragma unroll
-    for (int s = L - 1; s >= 0; s -= 2) {                                 // s = log2 of the round's first half-size
-      if (s >= 1) {
-        const int l2 = s - 1, h2 = 1 << l2;
-        const int low = t & (h2 - 1), base = ((t >> l2) << (l2 + 2)) | low;
-        if (s == L - 1) {                                                 // first round: from global memory, windowed
-          const int f = base >> L, p = base & (N - 1);
-          const float2* src = in + ((it.j0 + f0 + f) * H + p - n0);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            e[m] = make_double2(0.0, 0.0);
-            if (f < nfp) {
-              const float2 v = src[m * h2];
-              const double w = (double)window[p + m * h2];
-              e[m] = make_double2((double)v.x * w, (double)v.y * w);                // exact: 24 + 24 bits
-            }
-          }
-        } else {
-#pragma unroll
-          for (int m = 0; m < 4; ++m) e[m] = xs[base + m * h2];
+      for (int m = 0; m < 4; ++m) {
+        e[m] = make_double2(0.0, 0.0);
+        if (f < nfp) {
+          const float2 v = src[m * h2];
+          const double w = (double)window[p + m * h2];
+          e[m] = make_double2((double)v.x * w, (double)v.y * w);                // exact: 24 + 24 bits
         }
-        // one radix-4 butterfly = the two radix-2 stages: every value passes ONE twiddle product per round (-i is a swap)
-        const int i3 = (3 * low) << (L - 1 - s);
-        const double2 w1 = tw[low << (L - 1 - s)], w2 = tw[low << (L - s)], w3h = tw[i3 & (H - 1)];
-        const double2 w3 = i3 >= H ? make_double2(-w3h.x, -w3h.y) : w3h;         // the table holds half a turn
-        const double2 a = cadd(e[0], e[2]), b = cadd(e[1], e[3]), c = csub(e[0], e[2]), dm = csub(e[1], e[3]);
-        const double2 d = make_double2(dm.y, -dm.x);
-        e[0] = cadd(a, b);
-        e[1] = cmul(csub(a, b), w2);
-        e[2] = cmul(cadd(c, d), w1);
-        e[3] = cmul(csub(c, d), w3);
-        if (s >= 2) {
-#pragma unroll
-          for (int m = 0; m < 4; ++m) xs[base + m * h2] = e[m];
-          __syncthreads();
-        }
-      } else {                                                            // odd L: the last stage alone, slots 4 t .. 4 t + 3
-#pragma unroll
-        for (int m = 0; m < 4; ++m) e[m] = xs[4 * t + m];
-        const double2 a0 = cadd(e[0], e[1]), a1 = csub(e[0], e[1]), a2 = cadd(e[2], e[3]), a3 = csub(e[2], e[3]);
-        e[0] = a0, e[1] = a1, e[2] = a2, e[3] = a3;
       }
     }
+    fft_rounds<L>(e, xs, tw, t);
     // after the last round thread t holds slots 4 t .. 4 t + 3; slot q of a frame is bin bitrev_L(q)
 #pragma unroll
     for (int m = 0; m < 4; ++m) pw[4 * t + m] = e[m].x * e[m].x + e[m].y * e[m].y;
@@ -155,21 +126,10 @@ __global__ __launch_bounds__(256) void psd_measure_kernel(int N, const sy11_psd_
     if (noise) atomicAdd(&n_noise_s, 1);
   }
   __syncthreads();
-  for (int k = 2; k <= N; k <<= 1)                                        // bitonic sort, ascending; the non-noise slots (+inf) go last
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = t; i < N; i += 256) {
-        const int q = i ^ j;
-        if (q > i) {
-          const double a = srt[i], c = srt[q];
-          if (((i & k) == 0) ? (a > c) : (a < c)) srt[i] = c, srt[q] = a;
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort(srt, N, t);                                                // ascending; the non-noise slots (+inf) go last
   if (t != 0) return;
   const int n_noise = n_noise_s;
-  double med = __longlong_as_double(0x7ff8000000000000LL);
-  if (n_noise > 0) med = (n_noise & 1) ? srt[n_noise / 2] : ((srt[n_noise / 2 - 1] + srt[n_noise / 2]) * 0.5);
+  const double med = sorted_median(srt, n_noise);
   const double nd = (med * b.corr);
   double p_in = 0.0;
   for (int k = b.k_lo; k <= b.k_hi; ++k) p_in = (p_in + P[k + H]);
@@ -193,12 +153,6 @@ __global__ __launch_bounds__(256) void psd_measure_kernel(int N, const sy11_psd_
   int32_t* oi = out_i + (int64_t)blockIdx.x * 4;
   of[0] = p_in, of[1] = med, of[2] = sum_c, of[3] = sum_kc;
   oi[0] = k_dn, oi[1] = k_up, oi[2] = b.k_hi - b.k_lo + 1, oi[3] = n_noise;
-}
-
-inline int log2_fft(int n_fft) {
-  for (int l = 6; l <= 10; ++l)
-    if (n_fft == 1 << l) return l;
-  return 0;
 }
 
 }  // namespace

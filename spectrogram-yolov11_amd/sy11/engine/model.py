@@ -352,6 +352,13 @@ class YOLO:
         return measure_results(open_iq(source), results, sample_rate, center_freq, self.device, rows, n_fft, pad_f, beta, noise_band,
                                envelope, chunk_samples)
 
+    def characterize(self, extraction, n_fft=1024, min_rate=None, line_db=13.0):
+        """Characterise every clip of ``extraction`` (what ``extract`` returned) on the GPU -> ``sy11.data.characterize.Characterization``:
+        symbol rate, carrier offset at order 2 and 4, the decision between them, the fourth-order cumulant and the spectra of |x|^2, x^2
+        and x^4 (``DetectionPredictor.characterize``)."""
+        from ..data.characterize import characterize_extraction
+        return characterize_extraction(extraction, n_fft, min_rate, line_db)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

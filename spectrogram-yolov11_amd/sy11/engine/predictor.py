@@ -279,6 +279,18 @@ class DetectionPredictor:
         return measure_results(iq, results, sample_rate, center_freq, self.device, rows, n_fft, pad_f, beta, noise_band, envelope,
                                chunk_samples)
 
+    def characterize(self, extraction, n_fft=1024, min_rate=None, line_db=13.0):
+        """Say what kind of signal every clip of ``extraction`` (what ``extract`` returned) holds ->
+        ``sy11.data.characterize.Characterization``: per clip the Welch spectra (periodic Hann, ``n_fft`` in {64 .. 1024}, half-overlapped
+        frames from the clip's first sample) of |x|^2, x^2 and x^4, all clips in ONE launch and one reduction launch (``csrc/cyclo.hip``).
+        The line of |x|^2 gives the ``symbol_rate`` (searched from ``min_rate`` Hz up; ``keyed`` when it stands ``line_db`` dB above the median
+        floor), the lines of x^2 and x^4 the carrier's offset from the clip's centre at ``order`` 2 (BPSK, a bare carrier) or 4 (a
+        four-phase constellation), hence ``carrier``; ``c42`` is the normalised fourth-order cumulant and ``power`` the mean |x|^2.  The 13 dB
+        default of ``line_db`` is a judgement, not a measurement.  A clip shorter than ``n_fft`` is marked invalid.  Argument errors are
+        ``ValueError``s raised before anything touches the device; an empty extraction gives an empty ``Characterization`` with no launch."""
+        from ..data.characterize import characterize_extraction
+        return characterize_extraction(extraction, n_fft, min_rate, line_db)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

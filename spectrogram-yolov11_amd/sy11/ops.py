@@ -741,6 +741,121 @@ def psd_measure(partial, boxes, frac_lo, frac_hi):
     return psd, out_f, out_i
 
 
+def iq_cyclo(x, n_fft, items, window, twiddle, partial, mom):
+    """One launch of the characterisation kernel (sy11_iq_cyclo): every item of ``items`` — ``sy11.data.characterize.ITEM`` records (off, len,
+    j0, nf, row, last): the frames ``[j0, j0 + nf)`` of the clip ``x[off : off + len]``, all of one group of ``sy11_iq_cyclo_group()`` frames
+    — writes the sums of its frames' ``|FFT(w y_q)[k]|^2``, y = |x|^2, x^2, x^4, to ``partial[row]`` (rows, 3, n_fft) f32 and the sums of x^2
+    (re, im), |x|^2 and |x|^4 over the samples it owns to ``mom[row]`` (rows, 4) f64.  ``x``: the packed clips (``Extraction.packed``),
+    1-D contiguous complex64; a clip may start at an odd sample.  ``window`` / ``twiddle``: ``sy11.data.measure.tables_on``.  A refused call
+    raises ``Sy11Error`` and writes nothing.  -> ``(partial, mom)``."""
+    from .data.characterize import ITEM
+    from .data.measure import N_FFT
+    _need_gpu(x, window, twiddle, partial, mom)
+    n_fft = int(n_fft)
+    if n_fft not in N_FFT:
+        raise _lib.Sy11Error(f"iq_cyclo: n_fft must be one of {N_FFT}, got {n_fft}")
+    if x.dtype != torch.complex64 or x.dim() != 1 or not x.is_contiguous() or x.shape[0] == 0:
+        raise _lib.Sy11Error("iq_cyclo: x must be a non-empty 1-D contiguous complex64 device tensor")
+    n_in = x.shape[0]
+    if partial.dtype != torch.float32 or partial.dim() != 3 or tuple(partial.shape[1:]) != (3, n_fft) or partial.shape[0] == 0 \
+            or not partial.is_contiguous() or partial.device != x.device:
+        raise _lib.Sy11Error(f"iq_cyclo: `partial` must be a non-empty contiguous (rows, 3, {n_fft}) float32 tensor on x's device")
+    if mom.dtype != torch.float64 or tuple(mom.shape) != (partial.shape[0], 4) or not mom.is_contiguous() or mom.device != x.device:
+        raise _lib.Sy11Error(f"iq_cyclo: `mom` must be a contiguous ({partial.shape[0]}, 4) float64 tensor on x's device")
+    if window.dtype != torch.float32 or window.shape != (n_fft,) or not window.is_contiguous() or window.device != x.device \
+            or twiddle.dtype != torch.complex128 or twiddle.shape != (n_fft // 2,) or not twiddle.is_contiguous() or twiddle.device != x.device:
+        raise _lib.Sy11Error(f"iq_cyclo: `window` / `twiddle` must be the ({n_fft},) float32 and ({n_fft // 2},) complex128 tables on x's device")
+    if x.data_ptr() % 8 or window.data_ptr() % 4 or twiddle.data_ptr() % 16 or partial.data_ptr() % 4 or mom.data_ptr() % 8:
+        raise _lib.Sy11Error("iq_cyclo: x / mom must be 8-byte aligned, the twiddle table 16-byte, partial / window 4-byte")
+    it = np.ascontiguousarray(items)
+    if it.dtype != ITEM or it.ndim != 1 or it.shape[0] == 0:
+        raise _lib.Sy11Error("iq_cyclo: `items` must be a non-empty 1-D array of sy11.data.characterize.ITEM records")
+    if n_in >= 2 ** 31 or it.shape[0] >= 2 ** 31 or partial.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"iq_cyclo: len(x) = {n_in}, the {it.shape[0]} items and the {partial.shape[0]} rows must stay below 2^31 per call")
+    G, H = _lib.load().sy11_iq_cyclo_group(), n_fft // 2
+    off, ln, j0, nf, row = it["off"], it["len"], it["j0"].astype(np.int64), it["nf"].astype(np.int64), it["row"].astype(np.int64)
+    bad = (off < 0) | (ln < n_fft) | (ln > n_in) | (off > n_in - ln)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_cyclo: item {k}: the clip [{int(off[k])}, {int(off[k] + ln[k])}) is shorter than a frame or leaves the {n_in} "
+                             f"packed samples")
+    bad = (nf < 1) | (nf > G) | (j0 < 0) | (j0 // G != (j0 + nf - 1) // G)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_cyclo: item {k}: frames [{int(j0[k])}, {int(j0[k] + nf[k])}) are not 1 .. {G} frames of one group")
+    J = (ln - n_fft) // H + 1
+    bad = j0 + nf > J
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_cyclo: item {k}: frames [{int(j0[k])}, {int(j0[k] + nf[k])}) leave the clip's {int(J[k])} frames")
+    bad = (it["last"] != (j0 + nf == J))
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"iq_cyclo: item {k}: last = {int(it['last'][k])}, but its frames end at {int(j0[k] + nf[k])} of the clip's {int(J[k])}")
+    bad = (row < 0) | (row >= partial.shape[0])
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        k = int(np.flatnonzero(bad)[0]) if bad.any() else int(np.flatnonzero(np.bincount(row)[row] > 1)[0])
+        raise _lib.Sy11Error(f"iq_cyclo: item {k} writes row {int(row[k])} of a partial table of {partial.shape[0]} rows (a row takes one item)")
+    t = torch.from_numpy(it.view(np.uint8)).to(x.device)
+    call("sy11_iq_cyclo", n_fft, it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), _p(window),
+         C.c_void_p(torch.view_as_real(twiddle).data_ptr()), n_in, C.c_void_p(torch.view_as_real(x).data_ptr()), partial.shape[0], _p(partial),
+         _p(mom), _stream())
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return partial, mom
+
+
+CYCLO_OUT = 22                                                 # float64 per clip that sy11_cyclo_peaks writes (include/sy11.h)
+
+
+def cyclo_peaks(partial, mom, rows, n_clip, spectra=None, out=None):
+    """The reduction of a characterisation (sy11_cyclo_peaks), one launch: ``partial`` (rows, 3, n_fft) f32 and ``mom`` (rows, 4) f64 as
+    ``iq_cyclo`` filled them, ``rows`` — ``sy11.data.characterize.ROW`` records (row0, n_rows, clip, k_min, reserved, scale), one per clip to
+    reduce -> ``(spectra, out)``: (n_clip, 3, n_fft) float64 in signed-bin order and (n_clip, 22) float64 in the layout of include/sy11.h,
+    on the device.  Given ``spectra`` / ``out`` are written in the rows that ``rows`` names and left alone elsewhere; fresh ones are filled
+    with NaN first.  A refused call raises ``Sy11Error`` and writes nothing."""
+    from .data.characterize import ROW
+    from .data.measure import N_FFT
+    _need_gpu(partial, mom, spectra, out)
+    if partial.dtype != torch.float32 or partial.dim() != 3 or partial.shape[1] != 3 or partial.shape[2] not in N_FFT or partial.shape[0] == 0 \
+            or not partial.is_contiguous():
+        raise _lib.Sy11Error(f"cyclo_peaks: `partial` must be a non-empty contiguous (rows, 3, n_fft) float32 device tensor, n_fft one of {N_FFT}")
+    n_fft, H, dev = partial.shape[2], partial.shape[2] // 2, partial.device
+    if mom.dtype != torch.float64 or tuple(mom.shape) != (partial.shape[0], 4) or not mom.is_contiguous() or mom.device != dev:
+        raise _lib.Sy11Error(f"cyclo_peaks: `mom` must be a contiguous ({partial.shape[0]}, 4) float64 tensor on partial's device")
+    r = np.ascontiguousarray(rows)
+    n_clip = int(n_clip)
+    if r.dtype != ROW or r.ndim != 1 or r.shape[0] == 0 or r.shape[0] >= 2 ** 29 or not 0 < n_clip < 2 ** 31:
+        raise _lib.Sy11Error("cyclo_peaks: `rows` must be a non-empty 1-D array of sy11.data.characterize.ROW records (below 2^29) and n_clip positive")
+    for name, v, shape in (("spectra", spectra, (n_clip, 3, n_fft)), ("out", out, (n_clip, CYCLO_OUT))):
+        if v is not None and (v.dtype != torch.float64 or tuple(v.shape) != shape or not v.is_contiguous() or v.device != dev):
+            raise _lib.Sy11Error(f"cyclo_peaks: `{name}` must be None or a contiguous {shape} float64 tensor on partial's device")
+    bad = (r["n_rows"] < 1) | (r["row0"] < 0) | (r["row0"] + r["n_rows"] > partial.shape[0])
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"cyclo_peaks: clip {k} sums rows [{int(r['row0'][k])}, {int(r['row0'][k]) + int(r['n_rows'][k])}) of a partial table "
+                             f"of {partial.shape[0]} rows")
+    clip = r["clip"].astype(np.int64)
+    bad = (clip < 0) | (clip >= n_clip)
+    if bad.any() or np.unique(clip).shape[0] != clip.shape[0]:
+        k = int(np.flatnonzero(bad)[0]) if bad.any() else int(np.flatnonzero(np.bincount(clip)[clip] > 1)[0])
+        raise _lib.Sy11Error(f"cyclo_peaks: clip {k} writes output row {int(clip[k])} of {n_clip} (an output row takes one entry)")
+    bad = (r["k_min"] < 1) | (r["k_min"] > H - 1)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise _lib.Sy11Error(f"cyclo_peaks: clip {k}: the search range [{int(r['k_min'][k])}, {H - 1}] is empty or holds DC")
+    if not (np.isfinite(r["scale"]).all() and (r["scale"] > 0).all()):
+        raise _lib.Sy11Error("cyclo_peaks: scale must be positive and finite")
+    if spectra is None:
+        spectra = torch.full((n_clip, 3, n_fft), float("nan"), dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.full((n_clip, CYCLO_OUT), float("nan"), dtype=torch.float64, device=dev)
+    t = torch.from_numpy(r.view(np.uint8)).to(dev)
+    call("sy11_cyclo_peaks", n_fft, r.shape[0], C.c_void_p(r.ctypes.data), C.c_void_p(t.data_ptr()), partial.shape[0], _p(partial), _p(mom),
+         n_clip, _p(spectra), _p(out), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return spectra, out
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
