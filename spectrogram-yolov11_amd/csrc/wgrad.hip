@@ -838,6 +838,13 @@ extern "C" int sy11_conv2d_wgrad(const sy11_conv_desc* d, const void* x, const v
                                  void* stream) {
   SY11_REQUIRE(d && x && dy && dw, "conv2d_wgrad: null argument");
   SY11_REQUIRE(dtype_ok(d->dtype), "conv2d_wgrad: bad dtype");
+  // the geometry checks of the forward / input-gradient entry points (igemm.hip validate_conv): the tap table below is int8, so an
+  // offset past it would wrap and read the wrong pixels without any error
+  SY11_REQUIRE(d->B > 0 && d->IH > 0 && d->IW > 0 && d->C > 0 && d->N > 0 && d->KH > 0 && d->KW > 0, "conv2d_wgrad: non-positive dims");
+  SY11_REQUIRE(d->SH > 0 && d->SW > 0 && d->DH > 0 && d->DW > 0 && d->PH >= 0 && d->PW >= 0, "conv2d_wgrad: bad stride/dilation/pad");
+  SY11_REQUIRE(d->OH == (d->IH + 2 * d->PH - d->DH * (d->KH - 1) - 1) / d->SH + 1 && d->OW == (d->IW + 2 * d->PW - d->DW * (d->KW - 1) - 1) / d->SW + 1,
+               "conv2d_wgrad: OH/OW (%d,%d) do not match conv arithmetic", d->OH, d->OW);
+  SY11_REQUIRE(d->PH < 120 && d->DH * (d->KH - 1) < 120 && d->PW < 120 && d->DW * (d->KW - 1) < 120, "conv2d_wgrad: tap offset exceeds int8");
   hipStream_t st = (hipStream_t)stream;
   if (d->groups != 1 && d->groups == d->C && d->C == d->N) return sy11_conv2d_wgrad_dw(d, x, dy, dy_ld, dw, st);
   if (d->groups != 1) {                 // grouped: independent dense problems on channel slices; dw = [N][KH*KW][C/g]

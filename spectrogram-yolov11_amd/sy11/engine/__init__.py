@@ -11,6 +11,8 @@ what the data-parallel step all-reduces (one RCCL call over xGMI instead of per-
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 
 from typing import List, Optional
@@ -461,6 +463,22 @@ _CAPTURE_MODE = "thread_local"
 _MAX_FWD_GRAPHS = 8
 
 
+@contextlib.contextmanager
+def _no_gc_while_capturing():
+    """Collect cyclic garbage NOW and keep the collector off for the body.  A collection that starts in the middle of a capture runs
+    finalizers on the capturing thread: a dead model's graphs and their private pools (cycles through the tape's closures, so only the
+    collector frees them) are released with calls that are illegal while a stream captures, and the process aborts.  torch.cuda.graph
+    used to collect on entry and no longer does (torch.compiler.config.force_cudagraph_gc)."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
 class _Graphed:
     """One captured (forward graph, backward graph) pair for a fixed input signature of a module.
 
@@ -482,7 +500,7 @@ class _Graphed:
         self.is_list = is_list
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+        with _no_gc_while_capturing(), torch.cuda.stream(side):
             self.g_fwd = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_fwd, stream=side, capture_error_mode=_CAPTURE_MODE):
                 ec = Ctx(True, True, dtype, dev, store, module.__dict__.get("_sy11_pool_hint", 0))
@@ -532,7 +550,7 @@ class _GraphedFwd:
         self.static_in = [x.detach().clone() for x in xs]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+        with _no_gc_while_capturing(), torch.cuda.stream(side):
             self.g_fwd = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_fwd, stream=side, capture_error_mode=_CAPTURE_MODE):
                 ec = Ctx(module.training, False, dtype, dev, None, module.__dict__.get("_sy11_pool_hint", 0))
