@@ -267,7 +267,8 @@ template <typename T, int VEC, bool SILU>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long M, int C, const T* __restrict__ y, int y_ld, const T* __restrict__ dz, int dz_ld,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ scale, const float* __restrict__ shift,
-                                                            float* sum_g, float* sum_gx, int cpv, int rows_pb, int slots, const RowWalk w) {
+                                                            float* sum_g, float* sum_gx, int cpv, int rows_pb, int slots, int exclusive,
+                                                            const RowWalk w) {
   constexpr int U = 4;
   __shared__ float red[2][256][VEC > 1 ? VEC : 1];
   const RowLane l = row_lane<VEC>(cpv, rows_pb);
@@ -327,9 +328,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long M, int C, const
   }
   // dense atomics: lane t adds channel (cbase + t) -> one 256-byte request group per 64 lanes instead of VEC-strided scalars
   // (same-line atomic REQUESTS, not bytes, are what the memory side serialises)
-  // ordered mode: one row per workgroup x (slots == gridDim.x), every element of it written by exactly one workgroup (x, y): plain
-  // stores, and the host skips the zero fill
-  const bool exclusive = slots == (int)gridDim.x && slots > 1;
+  // ordered mode (`exclusive`, set by the host: never inferred from the slot count, a caller's own sum_slots may equal the grid): one row
+  // per workgroup x (slots == gridDim.x), every element of it written by exactly one workgroup (x, y): plain stores, and the host skips
+  // the zero fill
   for (int e = threadIdx.x; e < l.nch; e += 256) {
     const int cl2 = e / VEC, i2 = e - cl2 * VEC;
     const long ch = (long)(blockIdx.x % slots) * C + l.cbase + e;
@@ -339,7 +340,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long M, int C, const
   }
 }
 
-#define SY11_BNR(VV, SS) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, VV, SS>), grid, block, coef_bytes(g, VV, 3), st, (long)M, C, (const T*)y, y_ld, (const T*)dz, dz_ld, mean, rstd, scale, shift, sum_g, sum_gx, g.cpv, g.rows_pb, slots, w)
+#define SY11_BNR(VV, SS) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, VV, SS>), grid, block, coef_bytes(g, VV, 3), st, (long)M, C, (const T*)y, y_ld, (const T*)dz, dz_ld, mean, rstd, scale, shift, sum_g, sum_gx, g.cpv, g.rows_pb, slots, det ? 1 : 0, w)
 extern "C" int sy11_bn_act_bwd_reduce(int32_t dtype, int64_t M, int32_t C, const void* y, int32_t y_ld, const void* dz,
                                       int32_t dz_ld, const float* mean, const float* rstd, const float* scale,
                                       const float* shift, int32_t silu, float* sum_g, float* sum_gx, int32_t sum_slots,
@@ -377,6 +378,9 @@ extern "C" int sy11_bn_act_bwd_reduce(int32_t dtype, int64_t M, int32_t C, const
 }
 
 // pass 2: dy = gamma*rstd*(g - sum_g/M - xhat*sum_gx/M) = k0*g - k1 - (y - mean)*k2; block (0,*) also accumulates dgamma/dbeta
+// (M == 1, `single`: g == sum_g, the gradient is identically 0, and k0*g - k0*sum_g would leave the rounding of the two products
+// behind, 1e-5 at gamma*rstd ~ 800: there k1 holds sum_g itself and is taken from g before the multiplication; every other M keeps
+// the three-operation form, and with it the bits it always gave)
 // RES: the layer's output was also a residual sum (Bottleneck shortcut, block.py:725): the gradient of the residual operand is dz
 // itself — written (or added, f32 add, one rounding: what sy11_copy2d's accumulate does) from the dz values this pass holds anyway,
 // instead of a separate three-pass copy launch
@@ -389,6 +393,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, const 
                                                            float* dbeta, int cpv, int rows_pb, int slots, const RowWalk w, T* resg, int resg_ld,
                                                            int resg_acc) {
   constexpr int U = 4;
+  const bool single = M == 1;
   const RowLane l = row_lane<VEC>(cpv, rows_pb);
   float* s_sc = s_coef;
   float* s_sh = s_coef + l.cwv;
@@ -426,7 +431,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, const 
       s_sh[e] = shift[ch];
       s_mu[e] = mean[ch];
       s_k0[e] = gr;
-      s_k1[e] = gr * tg * invM;
+      s_k1[e] = single ? tg : gr * tg * invM;
       s_k2[e] = gr * tgx * invM * rs;
     }
   }
@@ -462,7 +467,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, const 
       for (int i = 0; i < VEC; ++i) {
         float g = vg[u][i];
         if (SILU) g *= dsilu_f(vy[u][i] * sc[i] + sh[i]);
-        vg[u][i] = k0[i] * g - k1[i] - (vy[u][i] - mu[i]) * k2[i];
+        vg[u][i] = single ? k0[i] * (g - k1[i]) - (vy[u][i] - mu[i]) * k2[i] : k0[i] * g - k1[i] - (vy[u][i] - mu[i]) * k2[i];
       }
       if (m + u * w.us < mend) vstore<T, VEC>(dy + (m + u * w.us) * dy_ld + l.c, vg[u]);
     }
