@@ -635,6 +635,74 @@ int sy11_iq_cyclo(int32_t n_fft, int32_t n_item, const sy11_cyclo_item* item_hos
 int sy11_cyclo_peaks(int32_t n_fft, int32_t n_row, const sy11_cyclo_row* row_host, const sy11_cyclo_row* row, int64_t n_rows,
                      const float* partial, const double* mom, int32_t n_clip, double* spectra, double* out, void* stream);
 
+/* ---- demodulation: the symbol stream and its error-vector magnitude of every clip of an extraction (spec in DESIGN.md §4) ----
+ * Feed-forward, three launches over all clips; the two fits between them are the caller's (sy11/data/demodulate.py).  A phase is an
+ * exact integer: sample n of a clip turns by (n W mod 2^64) 2^-64 cycles, whatever the tile it is computed in.
+ *
+ * Launch 1, sy11_iq_demod_filter.  An item is one tile of TILE = the value of sy11_iq_demod_tile usable samples [n0  n0 + cnt) of the
+ * clip in[off  off + len): the usable span is [hw  len - hw), n0 - hw a multiple of TILE, cnt = TILE except on the clip's last tile.
+ *   xr[n] = in[n] e^{-2 pi i (n wc mod 2^64) 2^-64}       y[n] = sum_{|k| <= hw} xr[n - k] taps[tap_off + hw + k]   (zeros outside the clip)
+ * in float64 (the taps ascending in -k, fused multiply-adds) and rounded ONCE to the float32 written to y[off + n] for the item's usable samples, and for n < hw by the
+ * item with first = 1, for n >= len - hw by the item with last = 1: the items of a clip write every y[n] of the clip once.  Per item
+ *   rows[row 3 + 0 .. 2] = Re, Im of sum |y[n]|^2 e^{-2 pi i (n ws mod 2^64) 2^-64} and sum |y[n]|^2 over its usable samples
+ * in float64 from the stored float32 y.  item: DEVICE table, item_host: its HOST copy, checked entry by entry before anything is launched:
+ * the clip lies inside in[0  n_in), n_taps = 2 hw + 1 <= 513 taps lie inside taps[0  n_tap), the tile is a tile of the usable span,
+ * first / last say what they must, and every row of rows[0  n_rows 3) is written by one item.  in, y: packed complex64 (a clip may
+ * start at an odd sample).  One fixed order for every sum; no atomics.  Nothing is launched on an error.
+ *
+ * Launch 2, sy11_demod_symbols.  An item is 1 .. 256 consecutive symbols of one clip: symbol i sits at t0 + i step = (k + mu) 2^32
+ * (Q32.32, mu cut to its top 24 bits) and is the 4-point cubic Lagrange interpolation of y[off + k - 1 .. k + 2] at mu, in float64 and rounded once, written
+ * to sym[sym_off + i].  rows[row 3 + 0 .. 2] = Re, Im of sum s_i^order (negated at order 4) and sum |s_i|^2, float64 from the stored s.
+ * Checked: 1 <= k <= len - 3 for every symbol, 2^32 <= step <= 2^40, the symbols inside sym[0  n_sym), order 2 or 4, one item per row.
+ *
+ * Launch 3, sy11_demod_decide.  An item is block b of the nb = ceil(n_sym / block) blocks of a clip's symbols sym[sym_off  sym_off + n_sym);
+ * theta[row0 + q] is the carrier phase at the centre q block + (n_q - 1) / 2 of block q.  phi_i is theta interpolated linearly between the
+ * centres and constant outside them, r_i = s_i e^{-i phi_i}, all in float64 and rounded once to float32 -> r[sym_off + i];
+ * d[sym_off + i] = (Re r < 0) at order 2, 2 (Re r < 0) + (Im r < 0) at order 4;  rows[(row0 + b) 3 + 0 .. 2] = sum |r|^2, sum Re(r conj(p)),
+ * n over the block, p the unit point that d names.  Checked: the symbols inside sym[0  n_sym), 8 <= block <= 256, nb and b as above, the
+ * rows inside the tables, order 2 or 4, one item per row.                                                                       */
+typedef struct sy11_demod_item {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip                                                              */
+  int64_t n0;                  /* first usable sample of the tile (index in the clip)                              */
+  int64_t tap_off;             /* first tap of the clip in the tap buffer                                          */
+  uint64_t wc;                 /* carrier: cycles per sample 2^64, wrapping                                        */
+  uint64_t ws;                 /* symbol rate: cycles per sample 2^64                                              */
+  int32_t cnt;                 /* usable samples of the tile, 1 .. TILE                                            */
+  int32_t hw;                  /* half width of the filter                                                         */
+  int32_t n_taps;              /* 2 hw + 1                                                                         */
+  int32_t row;                 /* row of the table the item writes                                                 */
+  int32_t first;               /* 1: the clip's first tile, which also writes y[0  hw); else 0                     */
+  int32_t last;                /* 1: the clip's last tile, which also writes y[len - hw  len); else 0              */
+} sy11_demod_item;
+typedef struct sy11_demod_block {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip                                                              */
+  int64_t t0;                  /* position of the item's first symbol, Q32.32 samples from the clip's first        */
+  int64_t step;                /* samples per symbol, Q32.32                                                       */
+  int64_t sym_off;             /* the item's first symbol in the packed symbol buffer                              */
+  int32_t n;                   /* symbols, 1 .. 256                                                                */
+  int32_t order;               /* 2 or 4                                                                           */
+  int32_t row;                 /* row of the table the item writes                                                 */
+  int32_t reserved;            /* 0                                                                                */
+} sy11_demod_block;
+typedef struct sy11_demod_dec {
+  int64_t sym_off;             /* the clip's first symbol in the packed symbol buffer                              */
+  int64_t n_sym;               /* symbols of the clip                                                              */
+  int64_t row0;                /* the clip's first row of theta and of the output table                            */
+  int32_t nb;                  /* blocks of the clip                                                               */
+  int32_t b;                   /* the item's block                                                                 */
+  int32_t block;               /* symbols per block, 8 .. 256                                                      */
+  int32_t order;               /* 2 or 4                                                                           */
+} sy11_demod_dec;
+int32_t sy11_iq_demod_tile(void);                 /* TILE: usable samples per item of launch 1, a constant of the build */
+int sy11_iq_demod_filter(int32_t n_item, const sy11_demod_item* item_host, const sy11_demod_item* item, int64_t n_tap, const float* taps,
+                         int64_t n_in, const float* in, float* y, int64_t n_rows, double* rows, void* stream);
+int sy11_demod_symbols(int32_t n_item, const sy11_demod_block* item_host, const sy11_demod_block* item, int64_t n_in, const float* y,
+                       int64_t n_sym, float* sym, int64_t n_rows, double* rows, void* stream);
+int sy11_demod_decide(int32_t n_item, const sy11_demod_dec* item_host, const sy11_demod_dec* item, int64_t n_sym, const float* sym,
+                      int64_t n_rows, const double* theta, float* r, uint8_t* d, double* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,9 @@ SIGNATURES = {
     "sy11_psd_measure": [_i32, _i32, _vp, _vp, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp],
     "sy11_iq_cyclo": [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_cyclo_peaks": [_i32, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
+    "sy11_iq_demod_filter": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "sy11_demod_symbols": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "sy11_demod_decide": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],
@@ -150,6 +153,7 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_iq_extract_tile": ([_i32], C.c_int32),
          "sy11_iq_psd_group": ([], C.c_int32),
          "sy11_iq_cyclo_group": ([], C.c_int32),
+         "sy11_iq_demod_tile": ([], C.c_int32),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}
 
 _lib = None

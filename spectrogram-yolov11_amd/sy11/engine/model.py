@@ -359,6 +359,14 @@ class YOLO:
         from ..data.characterize import characterize_extraction
         return characterize_extraction(extraction, n_fft, min_rate, line_db)
 
+    def demodulate(self, extraction, characterization=None, *, symbol_rate=None, offset=None, order=None, beta=0.35, span=8, block=32):
+        """Demodulate every clip of ``extraction`` on the GPU -> ``sy11.data.demodulate.Demodulation``: the symbol stream, the decisions and the
+        error-vector magnitude of every BPSK / four-phase clip, started from ``characterization`` (what ``characterize`` returned) or from
+        explicit ``symbol_rate`` / ``offset`` / ``order`` (``DetectionPredictor.demodulate``)."""
+        from ..data.demodulate import demodulate_extraction
+        return demodulate_extraction(extraction, characterization, symbol_rate=symbol_rate, offset=offset, order=order, beta=beta, span=span,
+                                     block=block)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

@@ -291,6 +291,21 @@ class DetectionPredictor:
         from ..data.characterize import characterize_extraction
         return characterize_extraction(extraction, n_fft, min_rate, line_db)
 
+    def demodulate(self, extraction, characterization=None, *, symbol_rate=None, offset=None, order=None, beta=0.35, span=8, block=32):
+        """Say what every clip of ``extraction`` (what ``extract`` returned) sent and how clean it was -> ``sy11.data.demodulate.Demodulation``:
+        per clip the corrected symbols, the decisions (``bits(i)``) and ``evm`` / ``mer_db``, feed-forward (``csrc/demod.hip``).  The symbol rate,
+        the carrier offset and the order (2: BPSK, 4: four-phase) of every clip come from ``characterization`` (what ``characterize``
+        returned for the same extraction) OR from ``symbol_rate`` / ``offset`` (Hz from the clip's centre) / ``order`` (scalars broadcast).  All
+        clips go through THREE launches: de-rotation, the root-raised-cosine matched filter (roll-off ``beta``, ``span`` symbols each side) and
+        the timing partials of every 512-sample tile; the symbols, interpolated at the instants of a line fitted through the tiles' timing
+        phases, with the sums of s^order per ``block`` symbols; the symbols turned back by the carrier phase tracked over the blocks, and
+        the decisions.  The stream is right up to a rotation by 2 pi / order (``phase_ambiguity``).  A clip that cannot be demodulated
+        (order not 2 or 4, not keyed, 2.5 <= fs / symbol_rate <= 16 violated, too short) is a row with ``valid`` False and a ``reason``.  Argument
+        errors are ``ValueError``s raised before anything touches the device; without a valid clip nothing is launched."""
+        from ..data.demodulate import demodulate_extraction
+        return demodulate_extraction(extraction, characterization, symbol_rate=symbol_rate, offset=offset, order=order, beta=beta, span=span,
+                                     block=block)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

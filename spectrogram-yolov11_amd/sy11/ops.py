@@ -856,6 +856,177 @@ def cyclo_peaks(partial, mom, rows, n_clip, spectra=None, out=None):
     return spectra, out
 
 
+def _first(bad):
+    return int(np.flatnonzero(bad)[0])
+
+
+def _one_item_per_row(what, row, n_rows):
+    """Raise unless every entry of ``row`` is a row of the table and named once."""
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        k = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise _lib.Sy11Error(f"{what}: item {k} writes row {int(row[k])} of a table of {n_rows} rows (a row takes one item)")
+
+
+def _packed_c64(what, name, v, like=None):
+    if v.dtype != torch.complex64 or v.dim() != 1 or not v.is_contiguous() or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or v.data_ptr() % 8 \
+            or (like is not None and (v.device != like.device or v.shape != like.shape or v.data_ptr() == like.data_ptr())):
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty 1-D contiguous 8-byte aligned complex64 device tensor below 2^31"
+                             + ("" if like is None else " of the input's length, on its device, and not the input itself"))
+
+
+def _row_table(what, name, v, dev):
+    if v.dtype != torch.float64 or v.dim() != 2 or v.shape[1] != 3 or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or not v.is_contiguous() or v.device != dev \
+            or v.data_ptr() % 8:
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty contiguous (rows, 3) float64 tensor on the input's device")
+
+
+def iq_demod_filter(x, items, taps, y, rows):
+    """Launch 1 of the demodulation (sy11_iq_demod_filter): every item of ``items`` — ``sy11.data.demodulate.ITEM`` records (off, len, n0, tap_off,
+    wc, ws, cnt, hw, n_taps, row, first, last): the tile ``[n0, n0 + cnt)`` of the usable span ``[hw, len - hw)`` of the clip ``x[off : off + len]`` —
+    de-rotates by ``wc``, filters with ``taps[tap_off : tap_off + n_taps]`` into ``y`` (packed like ``x``) and writes the timing partials at ``ws`` to
+    ``rows[row]`` (rows, 3) f64.  ``x``: the packed clips, 1-D contiguous complex64; a clip may start at an odd sample.  A refused call raises
+    ``Sy11Error`` and writes nothing.  -> ``(y, rows)``."""
+    from .data.demodulate import ITEM, MAX_TAPS
+    what = "iq_demod_filter"
+    _need_gpu(x, taps, y, rows)
+    _packed_c64(what, "x", x)
+    _packed_c64(what, "y", y, x)
+    _row_table(what, "rows", rows, x.device)
+    if taps.dtype != torch.float32 or taps.dim() != 1 or taps.shape[0] == 0 or taps.shape[0] >= 2 ** 31 or not taps.is_contiguous() or taps.device != x.device \
+            or taps.data_ptr() % 4:
+        raise _lib.Sy11Error(f"{what}: `taps` must be a non-empty 1-D contiguous float32 tensor on x's device")
+    it = np.ascontiguousarray(items)
+    if it.dtype != ITEM or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.demodulate.ITEM records")
+    T, n_in, n_tap = _lib.load().sy11_iq_demod_tile(), x.shape[0], taps.shape[0]
+    off, ln, n0, tap_off = it["off"], it["len"], it["n0"], it["tap_off"]
+    cnt, hw, n_taps, row = (it[k].astype(np.int64) for k in ("cnt", "hw", "n_taps", "row"))
+    bad = (off < 0) | (ln < 1) | (ln > n_in) | (off > n_in - ln)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: the clip [{int(off[k])}, {int(off[k] + ln[k])}) leaves the {n_in} packed samples")
+    bad = (hw < 1) | (n_taps != 2 * hw + 1) | (n_taps > MAX_TAPS)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: {int(n_taps[k])} taps for a half width of {int(hw[k])} (odd, 2 hw + 1, at most {MAX_TAPS})")
+    bad = (tap_off < 0) | (tap_off > n_tap - n_taps)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: taps [{int(tap_off[k])}, {int(tap_off[k] + n_taps[k])}) leave the {n_tap} packed taps")
+    bad = (n0 < hw) | ((n0 - hw) % T != 0) | (cnt < 1) | (cnt > T) | (n0 > ln - hw - cnt)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: samples [{int(n0[k])}, {int(n0[k] + cnt[k])}) are not a tile of the usable span [{int(hw[k])}, {int(ln[k] - hw[k])})")
+    bad = it["first"] != (n0 == hw)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: first = {int(it['first'][k])}, but it starts at {int(n0[k])} of the usable span from {int(hw[k])}")
+    is_last = n0 + cnt == ln - hw
+    bad = (it["last"] != is_last) | (~is_last & (cnt != T))
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: last = {int(it['last'][k])} with {int(cnt[k])} samples, but it ends at {int(n0[k] + cnt[k])} of the usable span "
+                             f"to {int(ln[k] - hw[k])}")
+    _one_item_per_row(what, row, rows.shape[0])
+    t = torch.from_numpy(it.view(np.uint8)).to(x.device)
+    call("sy11_iq_demod_filter", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_tap, _p(taps), n_in,
+         C.c_void_p(torch.view_as_real(x).data_ptr()), C.c_void_p(torch.view_as_real(y).data_ptr()), rows.shape[0], _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return y, rows
+
+
+def demod_symbols(y, items, sym, rows):
+    """Launch 2 of the demodulation (sy11_demod_symbols): every item of ``items`` — ``sy11.data.demodulate.BLOCK`` records (off, len, t0, step,
+    sym_off, n, order, row, reserved): ``n`` (1 .. 256) symbols of the clip ``y[off : off + len]`` at the Q32.32 positions ``t0 + i step`` — writes the
+    cubic interpolation of ``y`` at every position to ``sym[sym_off + i]`` and the sums of ``s^order`` (negated at order 4) and ``|s|^2`` to
+    ``rows[row]`` (rows, 3) f64.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``(sym, rows)``."""
+    from .data.demodulate import BLOCK
+    what = "demod_symbols"
+    _need_gpu(y, sym, rows)
+    _packed_c64(what, "y", y)
+    _packed_c64(what, "sym", sym)
+    if sym.device != y.device:
+        raise _lib.Sy11Error(f"{what}: `sym` must be on y's device")
+    _row_table(what, "rows", rows, y.device)
+    it = np.ascontiguousarray(items)
+    if it.dtype != BLOCK or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.demodulate.BLOCK records")
+    n_in, n_sym = y.shape[0], sym.shape[0]
+    off, ln, t0, step, sym_off = it["off"], it["len"], it["t0"], it["step"], it["sym_off"]
+    n, order, row = (it[k].astype(np.int64) for k in ("n", "order", "row"))
+    bad = (off < 0) | (ln < 4) | (ln > n_in) | (off > n_in - ln)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: the clip [{int(off[k])}, {int(off[k] + ln[k])}) leaves the {n_in} packed samples")
+    bad = (n < 1) | (n > 256) | (sym_off < 0) | (sym_off > n_sym - n)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: symbols [{int(sym_off[k])}, {int(sym_off[k] + n[k])}) are not 1 .. 256 of the {n_sym} packed symbols")
+    bad = (step < 2 ** 32) | (step > 2 ** 40) | (t0 < 2 ** 32) | (t0 >= ln * 2 ** 32)
+    bad = bad | (((t0 + (n - 1) * np.where(bad, 0, step)) >> 32) > ln - 3)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: positions from {int(t0[k])} in steps of {int(step[k])} (Q32.32) leave [1, {int(ln[k]) - 3}]")
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: order {int(order[k])} is not 2 or 4")
+    _one_item_per_row(what, row, rows.shape[0])
+    t = torch.from_numpy(it.view(np.uint8)).to(y.device)
+    call("sy11_demod_symbols", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_in, C.c_void_p(torch.view_as_real(y).data_ptr()),
+         n_sym, C.c_void_p(torch.view_as_real(sym).data_ptr()), rows.shape[0], _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(y.device))
+    return sym, rows
+
+
+def demod_decide(sym, items, theta, r, d, rows):
+    """Launch 3 of the demodulation (sy11_demod_decide): every item of ``items`` — ``sy11.data.demodulate.DEC`` records (sym_off, n_sym, row0, nb, b,
+    block, order): block ``b`` of the ``nb`` blocks of ``block`` symbols of the clip ``sym[sym_off : sym_off + n_sym]`` — turns its symbols back by the
+    phase interpolated from ``theta[row0 : row0 + nb]`` (float64, one per block, on the device) into ``r``, writes the decisions to ``d`` (uint8) and
+    the sums of ``|r|^2``, ``Re(r conj(point(d)))`` and the count to ``rows[row0 + b]`` (rows, 3) f64.  A refused call raises ``Sy11Error`` and writes
+    nothing.  -> ``(r, d, rows)``."""
+    from .data.demodulate import DEC
+    what = "demod_decide"
+    _need_gpu(sym, theta, r, d, rows)
+    _packed_c64(what, "sym", sym)
+    _packed_c64(what, "r", r, sym)
+    _row_table(what, "rows", rows, sym.device)
+    if theta.dtype != torch.float64 or tuple(theta.shape) != (rows.shape[0],) or not theta.is_contiguous() or theta.device != sym.device or theta.data_ptr() % 8:
+        raise _lib.Sy11Error(f"{what}: `theta` must be a contiguous ({rows.shape[0]},) float64 tensor on sym's device")
+    if d.dtype != torch.uint8 or tuple(d.shape) != tuple(sym.shape) or not d.is_contiguous() or d.device != sym.device:
+        raise _lib.Sy11Error(f"{what}: `d` must be a contiguous ({sym.shape[0]},) uint8 tensor on sym's device")
+    it = np.ascontiguousarray(items)
+    if it.dtype != DEC or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.demodulate.DEC records")
+    n_sym, n_rows = sym.shape[0], rows.shape[0]
+    sym_off, ns, row0 = it["sym_off"], it["n_sym"], it["row0"]
+    nb, b, block, order = (it[k].astype(np.int64) for k in ("nb", "b", "block", "order"))
+    bad = (ns < 1) | (sym_off < 0) | (sym_off > n_sym - ns)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: symbols [{int(sym_off[k])}, {int(sym_off[k] + ns[k])}) leave the {n_sym} packed symbols")
+    bad = (block < 8) | (block > 256) | (nb < 1) | (b < 0) | (b >= nb)
+    bad = bad | (nb != (ns + np.where(bad, 1, block) - 1) // np.where(bad, 1, block))
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: block {int(b[k])} of {int(nb[k])} blocks of {int(block[k])} does not fit {int(ns[k])} symbols")
+    bad = (row0 < 0) | (row0 > n_rows - nb)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: rows [{int(row0[k])}, {int(row0[k] + nb[k])}) leave a table of {n_rows} rows")
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: order {int(order[k])} is not 2 or 4")
+    _one_item_per_row(what, row0 + b, n_rows)
+    t = torch.from_numpy(it.view(np.uint8)).to(sym.device)
+    call("sy11_demod_decide", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_sym, C.c_void_p(torch.view_as_real(sym).data_ptr()),
+         n_rows, _p(theta), C.c_void_p(torch.view_as_real(r).data_ptr()), _p(d), _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(sym.device))
+    return r, d, rows
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
