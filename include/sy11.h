@@ -703,6 +703,65 @@ int sy11_demod_symbols(int32_t n_item, const sy11_demod_block* item_host, const 
 int sy11_demod_decide(int32_t n_item, const sy11_demod_dec* item_host, const sy11_demod_dec* item, int64_t n_sym, const float* sym,
                       int64_t n_rows, const double* theta, float* r, uint8_t* d, double* rows, void* stream);
 
+/* ---- frame search: where the sync words sit in the corrected symbols of every clip, and at which rotation (spec in DESIGN.md §4) ----
+ * Three launches over all clips; between the second and the third the caller compacts the hits (sy11/data/frames.py).  sym: the packed
+ * corrected symbols (complex64, what sy11_demod_decide wrote to r); words: packed DECISIONS of the words, one byte per symbol as d of
+ * sy11_demod_decide holds them (bit 0 at order 2; 2 b0 + b1 at order 4; higher bits ignored).  A decision w names the un-normalised point
+ * c = 1 - 2 w (order 2) or (1 - 2 (w >> 1)) + i (1 - 2 (w & 1)) (order 4), |c|^2 = order / 2.
+ *
+ * Launch 1, sy11_sync_correlate.  An item is one tile of TILE = the value of sy11_sync_tile positions [p0  p0 + cnt) of one pair (clip,
+ * word): the clip is sym[sym_off  sym_off + n_sym), the word words[word_off  word_off + L), the pair has P = n_sym - L + 1 positions, p0 is a
+ * multiple of TILE and cnt = TILE except on the pair's last tile.  For every position p, in float64 from the stored float32 symbols, k
+ * ascending, every product and sum rounded on its own:
+ *   Cr += re[p+k] Re c[k] + im[p+k] Im c[k]     Ci += im[p+k] Re c[k] - re[p+k] Im c[k]     E += re[p+k] re[p+k] + im[p+k] im[p+k]
+ *   rho2[pos_off + p] = (Cr Cr + Ci Ci) / ((order / 2) L E), 0 where E == 0
+ *   q[pos_off + p]    = Cr < 0 (order 2);  the index of the largest of (Cr, Ci, -Cr, -Ci), the lowest on a tie (order 4)
+ * item: DEVICE table, item_host: its HOST copy, checked entry by entry before anything is launched: order 2 or 4, the clip inside
+ * sym[0  n_sym), 8 <= L <= 256 and L <= n_sym, the word inside words[0  n_word), the tile a tile of [0  P), the pair's positions inside
+ * [0  n_pos), and no position written by two items.  One fixed order for every sum; no atomics.  Nothing is launched on an error.
+ *
+ * Launch 2, sy11_sync_peaks.  The same item table, checked in the same way.  hit[pos_off + p] = 1 iff rho2[p] >= threshold2, no p' of
+ * [p - L + 1  p) has rho2[p'] >= rho2[p] and no p' of (p  p + L - 1] has rho2[p'] > rho2[p] (windows clipped to [0  P)), else 0: of equal
+ * peaks closer than L the earliest is the hit; a NaN is never one and never suppresses one.  0 < threshold2 <= 1.
+ *
+ * Launch 3, sy11_sync_frames.  A frame is a hit: position p of a pair, with the rotation q that launch 1 found.  v[k] = sym[sym_off + p + k]
+ * turned back by q steps of 2 pi / order (negations and swaps: exact), decided as sy11_demod_decide decides, for k in [0  L + n_payload),
+ * n_payload = min(payload, n_sym - p - L).  rows[row 3 + 0 .. 2] = the word symbols whose decision differs, the bits that differ,
+ * n_payload.  bits[row stride  (row + 1) stride) = the payload's bits (1 per symbol at order 2; b0, b1 at order 4), MSB first, zeros after
+ * them.  Checked: order 2 or 4, q < order, the clip and the word inside their buffers, 8 <= L <= 256, p + L <= n_sym, 0 <= payload < 2^20
+ * and its ceil(payload log2(order) / 8) bytes inside a row of stride bytes, every row written by one frame.  bits may be null when stride
+ * is 0.                                                                                                                          */
+typedef struct sy11_sync_item {
+  int64_t sym_off;             /* the clip's first symbol in the packed symbol buffer                              */
+  int64_t n_sym;               /* symbols of the clip                                                              */
+  int64_t word_off;            /* the word's first decision in the packed word buffer                              */
+  int64_t pos_off;             /* the pair's first position in the packed position buffers                         */
+  int64_t p0;                  /* first position of the tile (index in the pair)                                   */
+  int32_t cnt;                 /* positions of the tile, 1 .. TILE                                                 */
+  int32_t L;                   /* symbols of the word, 8 .. 256                                                    */
+  int32_t order;               /* 2 or 4                                                                           */
+  int32_t reserved;            /* 0                                                                                */
+} sy11_sync_item;
+typedef struct sy11_sync_frame {
+  int64_t sym_off;             /* the clip's first symbol in the packed symbol buffer                              */
+  int64_t n_sym;               /* symbols of the clip                                                              */
+  int64_t word_off;            /* the word's first decision in the packed word buffer                              */
+  int64_t p;                   /* position of the word's first symbol in the clip                                  */
+  int32_t L;                   /* symbols of the word, 8 .. 256                                                    */
+  int32_t order;               /* 2 or 4                                                                           */
+  int32_t q;                   /* rotation: the symbols are turned back by q steps of 2 pi / order                 */
+  int32_t payload;             /* payload symbols asked for after the word, 0 .. 2^20 - 1                          */
+  int32_t row;                 /* row of the tables the frame writes                                               */
+  int32_t reserved;            /* 0                                                                                */
+} sy11_sync_frame;
+int32_t sy11_sync_tile(void);                     /* TILE: positions per item of launches 1 and 2, a constant of the build */
+int sy11_sync_correlate(int32_t n_item, const sy11_sync_item* item_host, const sy11_sync_item* item, int64_t n_word, const uint8_t* words,
+                        int64_t n_sym, const float* sym, int64_t n_pos, double* rho2, uint8_t* q, void* stream);
+int sy11_sync_peaks(int32_t n_item, const sy11_sync_item* item_host, const sy11_sync_item* item, int64_t n_word, int64_t n_sym, int64_t n_pos,
+                    const double* rho2, double threshold2, uint8_t* hit, void* stream);
+int sy11_sync_frames(int32_t n_frame, const sy11_sync_frame* frame_host, const sy11_sync_frame* frame, int64_t n_word, const uint8_t* words,
+                     int64_t n_sym, const float* sym, int64_t n_rows, int32_t* rows, int64_t stride, uint8_t* bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,9 @@ SIGNATURES = {
     "sy11_iq_demod_filter": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "sy11_demod_symbols": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "sy11_demod_decide": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "sy11_sync_correlate": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "sy11_sync_peaks": [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp],
+    "sy11_sync_frames": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],
@@ -154,6 +157,7 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_iq_psd_group": ([], C.c_int32),
          "sy11_iq_cyclo_group": ([], C.c_int32),
          "sy11_iq_demod_tile": ([], C.c_int32),
+         "sy11_sync_tile": ([], C.c_int32),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}
 
 _lib = None

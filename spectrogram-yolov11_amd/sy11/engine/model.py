@@ -367,6 +367,13 @@ class YOLO:
         return demodulate_extraction(extraction, characterization, symbol_rate=symbol_rate, offset=offset, order=order, beta=beta, span=span,
                                      block=block)
 
+    def find_frames(self, demodulation, words, *, payload=0, threshold=0.8, max_errors=None, t0=None):
+        """Find the sync ``words`` in every clip of ``demodulation`` on the GPU -> ``sy11.data.frames.Frames``: per frame its clip, word, position, the
+        rotation that resolves the demodulator's phase ambiguity, the word's errors and ``payload`` symbols' bits
+        (``DetectionPredictor.find_frames``)."""
+        from ..data.frames import find_frames
+        return find_frames(demodulation, words, payload=payload, threshold=threshold, max_errors=max_errors, t0=t0)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

@@ -306,6 +306,20 @@ class DetectionPredictor:
         return demodulate_extraction(extraction, characterization, symbol_rate=symbol_rate, offset=offset, order=order, beta=beta, span=span,
                                      block=block)
 
+    def find_frames(self, demodulation, words, *, payload=0, threshold=0.8, max_errors=None, t0=None):
+        """Say where framed data starts in every clip of ``demodulation`` (what ``demodulate`` returned) and at which of the ``order`` rotations the
+        demodulator landed -> ``sy11.data.frames.Frames``, one row per frame sorted by (clip, word, position) (``csrc/framesync.hip``).  ``words``: the
+        sync words, each a sequence of 0/1 bits, first bit first, mapped to symbols as ``Demodulation.bits`` maps them.  All clips and words go
+        through THREE launches: the normalised correlation ``rho`` of the corrected symbols with every word at every position, in float64
+        and one fixed order; its peaks at or above ``threshold`` (of equal peaks closer than a word the earliest); and, for every peak, the
+        word's symbol and bit errors after turning the symbols back by the peak's rotation and ``payload`` symbols' bits after the word,
+        packed on the device (``Frames.payload_bits(k)``).  ``max_errors`` drops frames with more word symbol errors; ``t0`` (per clip, seconds:
+        ``extraction.t0``) is added to ``time``.  A pair (clip, word) that cannot be searched (clip not valid, bit count not divisible by
+        log2(order), word outside 8 .. 256 symbols or longer than the clip) is listed in ``Frames.pairs`` with a reason.  Argument errors are
+        ``ValueError``s raised before anything touches the device; without a valid pair nothing is launched."""
+        from ..data.frames import find_frames
+        return find_frames(demodulation, words, payload=payload, threshold=threshold, max_errors=max_errors, t0=t0)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

@@ -1027,6 +1027,160 @@ def demod_decide(sym, items, theta, r, d, rows):
     return r, d, rows
 
 
+def _u8_vector(what, name, v, dev, n=None):
+    if v.dtype != torch.uint8 or v.dim() != 1 or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or not v.is_contiguous() or v.device != dev \
+            or (n is not None and v.shape[0] != n):
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty 1-D contiguous uint8 tensor on the symbols' device" + ("" if n is None else f" of {n} entries"))
+
+
+def _sync_items(what, items, n_sym, n_word, n_pos):
+    """The checks ``sync_correlate`` and ``sync_peaks`` share (the library repeats them) -> the contiguous ``ITEM`` table."""
+    from .data.frames import ITEM, L_MAX, L_MIN
+    it = np.ascontiguousarray(items)
+    if it.dtype != ITEM or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.frames.ITEM records")
+    T = _lib.load().sy11_sync_tile()
+    sym_off, ns, word_off, pos_off, p0 = it["sym_off"], it["n_sym"], it["word_off"], it["pos_off"], it["p0"]
+    cnt, L, order = (it[k].astype(np.int64) for k in ("cnt", "L", "order"))
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: order {int(order[k])} is not 2 or 4")
+    bad = (sym_off < 0) | (ns < 1) | (ns > n_sym) | (sym_off > n_sym - ns)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: the clip [{int(sym_off[k])}, {int(sym_off[k] + ns[k])}) leaves the {n_sym} packed symbols")
+    bad = (L < L_MIN) | (L > L_MAX) | (L > ns)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: a word of {int(L[k])} symbols is not {L_MIN} .. {L_MAX} of a clip of {int(ns[k])}")
+    bad = (word_off < 0) | (word_off > n_word - L)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: the word [{int(word_off[k])}, {int(word_off[k] + L[k])}) leaves the {n_word} packed word symbols")
+    P = ns - L + 1
+    bad = (p0 < 0) | (p0 % T != 0) | (cnt < 1) | (cnt > T) | (p0 > P - cnt) | ((cnt != T) & (p0 + cnt != P))
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: positions [{int(p0[k])}, {int(p0[k] + cnt[k])}) are not a tile of [0, {int(P[k])})")
+    bad = (pos_off < 0) | (pos_off > n_pos - P)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: positions [{int(pos_off[k])}, {int(pos_off[k] + P[k])}) leave the {n_pos} packed positions")
+    a = pos_off + p0
+    o = np.argsort(a, kind="stable")
+    bad = (a + cnt)[o][:-1] > a[o][1:]
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {int(o[k + 1])} writes position {int(a[o][k + 1])}, which item {int(o[k])} of this call writes")
+    return it
+
+
+def sync_correlate(sym, items, words, rho2, q):
+    """Launch 1 of the frame search (sy11_sync_correlate): every item of ``items`` — ``sy11.data.frames.ITEM`` records (sym_off, n_sym, word_off, pos_off,
+    p0, cnt, L, order, reserved): the positions ``[p0, p0 + cnt)`` of the ``n_sym - L + 1`` of the clip ``sym[sym_off : sym_off + n_sym]`` against the word
+    ``words[word_off : word_off + L]`` (uint8 decisions) — writes the squared normalised correlation to ``rho2[pos_off + p]`` (float64) and the rotation to
+    ``q[pos_off + p]`` (uint8).  ``sym``: the packed corrected symbols, 1-D contiguous complex64.  A refused call raises ``Sy11Error`` and writes
+    nothing.  -> ``(rho2, q)``."""
+    what = "sync_correlate"
+    _need_gpu(sym, words, rho2, q)
+    _packed_c64(what, "sym", sym)
+    _u8_vector(what, "words", words, sym.device)
+    if rho2.dtype != torch.float64 or rho2.dim() != 1 or rho2.shape[0] == 0 or rho2.shape[0] >= 2 ** 31 or not rho2.is_contiguous() or rho2.device != sym.device \
+            or rho2.data_ptr() % 8:
+        raise _lib.Sy11Error(f"{what}: `rho2` must be a non-empty 1-D contiguous float64 tensor on the symbols' device")
+    _u8_vector(what, "q", q, sym.device, rho2.shape[0])
+    it = _sync_items(what, items, sym.shape[0], words.shape[0], rho2.shape[0])
+    t = torch.from_numpy(it.view(np.uint8)).to(sym.device)
+    call("sy11_sync_correlate", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), words.shape[0], _p(words), sym.shape[0],
+         C.c_void_p(torch.view_as_real(sym).data_ptr()), rho2.shape[0], _p(rho2), _p(q), _stream())
+    t.record_stream(torch.cuda.current_stream(sym.device))
+    return rho2, q
+
+
+def sync_peaks(rho2, items, threshold2, hit, n_sym, n_word):
+    """Launch 2 of the frame search (sy11_sync_peaks): over the item table of launch 1 (checked again, against ``n_sym`` symbols and ``n_word`` word
+    symbols), ``hit[pos_off + p] = 1`` where ``rho2`` is at least ``threshold2`` (the SQUARED threshold, in (0, 1]), no earlier position within ``L - 1`` is at
+    least as large and no later one within ``L - 1`` larger; else 0.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``hit``."""
+    what = "sync_peaks"
+    _need_gpu(rho2, hit)
+    if rho2.dtype != torch.float64 or rho2.dim() != 1 or rho2.shape[0] == 0 or rho2.shape[0] >= 2 ** 31 or not rho2.is_contiguous() or rho2.data_ptr() % 8:
+        raise _lib.Sy11Error(f"{what}: `rho2` must be a non-empty 1-D contiguous float64 device tensor")
+    _u8_vector(what, "hit", hit, rho2.device, rho2.shape[0])
+    if isinstance(threshold2, bool) or not isinstance(threshold2, (int, float, np.integer, np.floating)) or not 0.0 < float(threshold2) <= 1.0:
+        raise _lib.Sy11Error(f"{what}: the squared threshold {threshold2!r} is not in (0, 1]")
+    n_sym, n_word = int(n_sym), int(n_word)
+    if not (0 < n_sym < 2 ** 31 and 0 < n_word < 2 ** 31):
+        raise _lib.Sy11Error(f"{what}: need symbols and word symbols, each below 2^31 (n_sym={n_sym} n_word={n_word})")
+    it = _sync_items(what, items, n_sym, n_word, rho2.shape[0])
+    t = torch.from_numpy(it.view(np.uint8)).to(rho2.device)
+    call("sy11_sync_peaks", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_word, n_sym, rho2.shape[0], _p(rho2), float(threshold2), _p(hit),
+         _stream())
+    t.record_stream(torch.cuda.current_stream(rho2.device))
+    return hit
+
+
+def sync_frames(sym, frames, words, rows, bits):
+    """Launch 3 of the frame search (sy11_sync_frames): every frame of ``frames`` — ``sy11.data.frames.FRAME`` records (sym_off, n_sym, word_off, p, L,
+    order, q, payload, row, reserved): the word ``words[word_off : word_off + L]`` at position ``p`` of the clip ``sym[sym_off : sym_off + n_sym]``, turned back
+    by ``q`` steps of 2 pi / order — writes (errors, bit_errors, n_payload) to ``rows[row]`` (rows, 3) int32 and the packed payload bits, zero-padded, to
+    ``bits[row]`` (rows, stride) uint8.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``(rows, bits)``."""
+    from .data.frames import FRAME, L_MAX, L_MIN, PAYLOAD_MAX
+    what = "sync_frames"
+    _need_gpu(sym, words, rows, bits)
+    _packed_c64(what, "sym", sym)
+    _u8_vector(what, "words", words, sym.device)
+    if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 3 or rows.shape[0] == 0 or rows.shape[0] >= 2 ** 31 or not rows.is_contiguous() \
+            or rows.device != sym.device or rows.data_ptr() % 4:
+        raise _lib.Sy11Error(f"{what}: `rows` must be a non-empty contiguous (rows, 3) int32 tensor on the symbols' device")
+    if bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[0] != rows.shape[0] or bits.shape[1] > PAYLOAD_MAX // 4 or not bits.is_contiguous() \
+            or bits.device != sym.device:
+        raise _lib.Sy11Error(f"{what}: `bits` must be a contiguous ({rows.shape[0]}, stride) uint8 tensor on the symbols' device, stride at most {PAYLOAD_MAX // 4}")
+    fr = np.ascontiguousarray(frames)
+    if fr.dtype != FRAME or fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `frames` must be a non-empty 1-D array of sy11.data.frames.FRAME records")
+    n_sym, n_word, n_rows, stride = sym.shape[0], words.shape[0], rows.shape[0], bits.shape[1]
+    sym_off, ns, word_off, p = fr["sym_off"], fr["n_sym"], fr["word_off"], fr["p"]
+    L, order, q, payload, row = (fr[k].astype(np.int64) for k in ("L", "order", "q", "payload", "row"))
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: order {int(order[k])} is not 2 or 4")
+    bad = (q < 0) | (q >= order)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: rotation {int(q[k])} is not below the order {int(order[k])}")
+    bad = (sym_off < 0) | (ns < 1) | (ns > n_sym) | (sym_off > n_sym - ns)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: the clip [{int(sym_off[k])}, {int(sym_off[k] + ns[k])}) leaves the {n_sym} packed symbols")
+    bad = (L < L_MIN) | (L > L_MAX) | (L > ns)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: a word of {int(L[k])} symbols is not {L_MIN} .. {L_MAX} of a clip of {int(ns[k])}")
+    bad = (word_off < 0) | (word_off > n_word - L)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: the word [{int(word_off[k])}, {int(word_off[k] + L[k])}) leaves the {n_word} packed word symbols")
+    bad = (p < 0) | (p > ns - L)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: the word at position {int(p[k])} ends after the clip's {int(ns[k])} symbols")
+    bad = (payload < 0) | (payload >= PAYLOAD_MAX) | ((payload * (order // 2) + 7) // 8 > stride)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: the bits of {int(payload[k])} payload symbols leave the {stride} bytes of a row")
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        k = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise _lib.Sy11Error(f"{what}: frame {k} writes row {int(row[k])} of a table of {n_rows} rows (a row takes one frame)")
+    t = torch.from_numpy(fr.view(np.uint8)).to(sym.device)
+    call("sy11_sync_frames", fr.shape[0], C.c_void_p(fr.ctypes.data), C.c_void_p(t.data_ptr()), n_word, _p(words), n_sym,
+         C.c_void_p(torch.view_as_real(sym).data_ptr()), n_rows, _p(rows), stride, _p(bits) if stride else None, _stream())
+    t.record_stream(torch.cuda.current_stream(sym.device))
+    return rows, bits
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
