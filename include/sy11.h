@@ -378,7 +378,10 @@ int sy11_opt_step(const sy11_opt_desc* d, float* param, float* grad, float* mom,
 /* ---- IQ -> STFT -> power -> mel -> log producer (no reference code: README.md:7; spec in DESIGN.md) ------ */
 /* iq: (B, L) interleaved complex64; db: (B, n_frames, n_mel) f32 dB (frame-major: coalesced stores);
  * minmax: (B,2) f32 [min,max] per image
- * (must be pre-filled with +inf/-inf by the caller or by sy11_stft_minmax_init).                            */
+ * (must be pre-filled with +inf/-inf by the caller or by sy11_stft_minmax_init).
+ * n_fft: a power of two in [64, 8192].  window: n_fft f32 taps; mel_start: n_mel int32 first bins (0 <= start < n_fft);
+ * mel_w: (n_mel, mel_taps) f32, a tap at bin >= n_fft does not exist (zero padding may follow the last real tap); with n_fft = 1024 and
+ * mel_taps = 8 mel_w must be 16-byte aligned.                                                                  */
 int sy11_stft_logmel(int32_t B, int32_t L, int32_t n_fft, int32_t hop, int32_t n_frames, int32_t n_mel,
                      const float* iq, const float* window, const int32_t* mel_start, const float* mel_w,
                      int32_t mel_taps, float* db, float* minmax, void* stream);

@@ -21,6 +21,11 @@ __device__ __forceinline__ void atomic_max_f(float* p, float v) {
   if (v >= 0.f) atomicMax((int*)p, __float_as_int(v)); else atomicMin((unsigned*)p, __float_as_uint(v));
 }
 
+// 10 log10(p + 1e-10) of the two general kernels, rounded once: `10.0f * log10f(x)` rounds the logarithm (1 - 2 ulp of a value near 10 for a
+// strong signal) and then multiplies that error by 10, which is several times the half ulp of the dB value itself — the largest term of
+// these kernels' error at a frame's peak bin.  The wave kernel keeps its v_log_f32 form: it is the product shape's.
+__device__ __forceinline__ float db_of(float p) { return (float)(10.0 * log10((double)p + 1e-10)); }
+
 __global__ __launch_bounds__(256) void stft_logmel_kernel(int L, int n_fft, int log2n, int hop, int n_frames, int n_mel, const float2* __restrict__ iq,
                                                           const float* __restrict__ window, const int* __restrict__ mel_start,
                                                           const float* __restrict__ mel_w, int mel_taps, float* __restrict__ db, float* __restrict__ minmax) {
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(int L, int n_fft, int 
       const int k = k0 + t;
       if (w != 0.f && k < n_fft) acc += w * re[(k + hshift) & hmask];
     }
-    const float v = 10.0f * log10f(acc + 1e-10f);
+    const float v = db_of(acc);
     out[j] = v;
     lmin = fminf(lmin, v); lmax = fmaxf(lmax, v);
   }
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(256) void stft_logmel1024_kernel(int L, int hop, in
           if (w != 0.f && kk < N) acc += w * pw[(kk + N / 2) & (N - 1)];
         }
       }
-      const float val = 10.0f * log10f(acc + 1e-10f);
+      const float val = db_of(acc);
       o[j] = val;
       lmin = fminf(lmin, val); lmax = fmaxf(lmax, val);
     }
@@ -418,7 +423,13 @@ extern "C" int sy11_stft_logmel(int32_t B, int32_t L, int32_t n_fft, int32_t hop
     return SY11_OK;
   }
   const size_t lds = (size_t)3 * n_fft * sizeof(float);
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)stft_logmel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 64 * 1024) {                                     // n_fft = 8192: 96 KiB of dynamic LDS has to be asked for
+    const hipError_t e = hipFuncSetAttribute((const void*)stft_logmel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      SY11_FAIL(SY11_ELAUNCH, "stft_logmel: n_fft = %d needs %zu bytes of LDS per workgroup: %s", n_fft, lds, hipGetErrorString(e));
+    }
+  }
   hipLaunchKernelGGL(stft_logmel_kernel, dim3(n_frames, B), dim3(256), lds, st, L, n_fft, log2n, hop, n_frames, n_mel, (const float2*)iq, window,
                      mel_start, mel_w, mel_taps, db, minmax);
   SY11_LAUNCH_CHECK("stft_logmel");

@@ -423,6 +423,14 @@ def stft_logmel(iq, window, mel_start, mel_w, n_fft, hop, n_frames, n_mel):
     _need_gpu(iq, window, mel_start, mel_w)
     if iq.dtype != torch.complex64 or not iq.is_contiguous():
         raise _lib.Sy11Error("stft_logmel: iq must be contiguous complex64")
+    # the tables go down as raw pointers: another dtype or a strided view would be reinterpreted, not converted
+    if window.dtype != torch.float32 or tuple(window.shape) != (n_fft,) or not window.is_contiguous():
+        raise _lib.Sy11Error(f"stft_logmel: `window` must be a contiguous f32 vector of n_fft = {n_fft} taps, got {window.dtype} {tuple(window.shape)}")
+    if mel_start.dtype != torch.int32 or tuple(mel_start.shape) != (n_mel,) or not mel_start.is_contiguous():
+        raise _lib.Sy11Error(f"stft_logmel: `mel_start` must be a contiguous int32 vector of n_mel = {n_mel} bins, got {mel_start.dtype} "
+                             f"{tuple(mel_start.shape)}")
+    if mel_w.dtype != torch.float32 or mel_w.dim() != 2 or mel_w.shape[0] != n_mel or mel_w.shape[1] < 1 or not mel_w.is_contiguous():
+        raise _lib.Sy11Error(f"stft_logmel: `mel_w` must be a contiguous f32 (n_mel = {n_mel}, taps) matrix, got {mel_w.dtype} {tuple(mel_w.shape)}")
     B, L = iq.shape
     db = torch.empty((B, n_frames, n_mel), dtype=torch.float32, device=iq.device)
     mm = torch.empty((B, 2), dtype=torch.float32, device=iq.device)
