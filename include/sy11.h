@@ -765,6 +765,65 @@ int sy11_sync_peaks(int32_t n_item, const sy11_sync_item* item_host, const sy11_
 int sy11_sync_frames(int32_t n_frame, const sy11_sync_frame* frame_host, const sy11_sync_frame* frame, int64_t n_word, const uint8_t* words,
                      int64_t n_sym, const float* sym, int64_t n_rows, int32_t* rows, int64_t stride, uint8_t* bits, void* stream);
 
+/* ---- frame decoding: soft bits, the Viterbi decoder of the rate 1/2, K = 7 code, de-whitening and CRC of every frame (spec in DESIGN.md §4) ----
+ * Three launches over all frames (sy11/data/decode.py).  A frame's received stream starts at symbol sym_off of the packed corrected symbols
+ * sym (complex64, what sy11_demod_decide wrote to r): the first symbol after its sync word.  w = log2(order) bits per symbol.  A frame has T
+ * trellis steps, 1 <= T <= T_MAX = 8192, the value of sy11_fec_tmax, T >= 7 with a tail, and writes row `row` of every table of the call:
+ * soft (n_rows, stride_soft) int8, bits (n_rows, stride_bits) uint8, out (n_rows, 2) int32, data (n_rows, stride_data) uint8, rows (n_rows, 5)
+ * int32.  frame: DEVICE table, frame_host: its HOST copy, checked entry by entry before anything is launched: order 2 or 4, q < order, tail 0
+ * or 1, T in range, the row inside the tables and written by one frame of the call, and what each launch adds below.  Nothing is launched on
+ * an error.  Everything after the quantiser is integer arithmetic; no atomics; a frame's result does not depend on the other frames.
+ *
+ * The code: generators g0, g1, 7-bit integers with bits 6 and 0 set.  With input bit u_t and state s (6 bits, the newest input at bit 5):
+ * R = (u_t << 6) | s, c[2t + j] = parity(R & g_j), next state R >> 1; the encoder starts in state 0.  With a tail the last 6 inputs are 0.
+ *
+ * Launch 1, sy11_fec_soft.  pattern: the puncture pattern over the mother stream c[0], c[1], ..., bit i of the word = position i, 1 = sent,
+ * applied with the even period 2 .. 64 (nothing removed: period 2, pattern 3); at least one 1, none at or above `period`.  With `ones` the 1s of
+ * a period, mother position j = full period + at holds received bit m = full ones + popcount(pattern & ((1 << at) - 1)) when bit `at` is set,
+ * and an erasure otherwise.  Received bit m is component m % w (Re; Re then Im at order 4) of symbol m / w turned back by q steps of
+ * 2 pi / order (negations and swaps: exact).  soft[row stride_soft + j] = clamp(rintf(x scale), -127, 127) for the float32 component x, ONE
+ * float32 multiplication, 0 for a NaN product and for an erasure, j in [0  2T).  Positive means bit 0.  Checked too: the frame's
+ * ceil(n_coded / w) symbols inside sym[0  n_sym), n_coded = the 1s of the pattern over [0  2T); 2T <= stride_soft (even); scale finite, > 0.
+ *
+ * Launch 2, sy11_fec_viterbi.  int32 path metrics, PM(0) = 0, PM(s != 0) = -2^30.  Step t, next state s', b in {0, 1}: R_b = (s' << 1) | b,
+ * bm_b = sum_j (1 - 2 parity(R_b & g_j)) y[2t + j], m_b = PM(R_b & 63) + bm_b; d_t(s') = m_1 > m_0 (a tie keeps b = 0), PM'(s') = max(m_0, m_1).
+ * No normalisation: |PM| <= 254 * 8192 + 2^30.  End state: 0 with a tail, else the state of the largest final metric, the lowest on a tie.
+ * Traceback for t = T - 1 .. 0: u_t = s >> 5, s = ((s << 1) | d_t(s)) & 63.  bits[row stride_bits ...] = u_0 .. u_(T-1) packed MSB first,
+ * zeros after them; out[2 row + 0 .. 1] = the end state's final metric, the end state.  One wavefront per frame, lane = state; 8 max(T) bytes
+ * of dynamic LDS.  Checked too: the generators, 2T <= stride_soft (even, soft 2-byte aligned), ceil(T / 8) <= stride_bits.
+ *
+ * Launch 3, sy11_fec_check.  c^ = u_0 .. u_(T-1) encoded again from state 0.  n_channel = #{j : y[j] != 0}, channel_errors = #{j : y[j] != 0
+ * and (y[j] < 0) != c^[j]}.  v_t = u_t ^ whiten[t], t < n_info (whiten: DEVICE, n_info bytes of 0 / 1, or null); data[row stride_data ...] = v
+ * packed MSB first, zeros after them.  crc: HOST, the Rocksoft model; width 0 = none, else 8 .. 32 and n_info > width.  crc_recv = the last
+ * `width` bits of v read MSB first; crc_calc runs over the n_info - width bits before them (with refin each group of 8 bits LSB first, and
+ * the count a multiple of 8).  rows[5 row + 0 .. 4] = crc_calc, crc_recv (both uint32 bit patterns), crc_ok (1 / 0, -1 without a crc),
+ * channel_errors, n_channel.  Checked too: T = n_info + 6 tail for every frame, the strides, the generators, the crc's fields.          */
+typedef struct sy11_fec_frame {
+  int64_t sym_off;             /* the frame's first payload symbol in the packed symbol buffer (launch 1 alone reads it) */
+  int32_t T;                   /* trellis steps, 1 .. T_MAX (7 .. T_MAX with a tail)                                */
+  int32_t order;               /* 2 or 4                                                                           */
+  int32_t q;                   /* rotation: the symbols are turned back by q steps of 2 pi / order                 */
+  int32_t tail;                /* 1: the last 6 inputs are 0 and the end state is 0; 0: the end state is free      */
+  int32_t row;                 /* row of the tables the frame writes                                               */
+  float scale;                 /* soft values per unit of a symbol's component (launch 1 alone reads it)           */
+} sy11_fec_frame;
+typedef struct sy11_fec_crc {
+  int32_t width;               /* 0: no check; else 8 .. 32                                                        */
+  uint32_t poly;               /* without the top bit                                                              */
+  uint32_t init;
+  uint32_t xorout;
+  int32_t refin;               /* 0 or 1                                                                           */
+  int32_t refout;              /* 0 or 1                                                                           */
+} sy11_fec_crc;
+int32_t sy11_fec_tmax(void);                      /* T_MAX: the trellis steps of a frame at the most, a constant of the build */
+int sy11_fec_soft(int32_t n_frame, const sy11_fec_frame* frame_host, const sy11_fec_frame* frame, int32_t period, uint64_t pattern, int64_t n_sym,
+                  const float* sym, int64_t n_rows, int64_t stride_soft, int8_t* soft, void* stream);
+int sy11_fec_viterbi(int32_t n_frame, const sy11_fec_frame* frame_host, const sy11_fec_frame* frame, int32_t g0, int32_t g1, int64_t n_rows,
+                     int64_t stride_soft, const int8_t* soft, int64_t stride_bits, uint8_t* bits, int32_t* out, void* stream);
+int sy11_fec_check(int32_t n_frame, const sy11_fec_frame* frame_host, const sy11_fec_frame* frame, int32_t g0, int32_t g1, int32_t n_info,
+                   const uint8_t* whiten, const sy11_fec_crc* crc, int64_t n_rows, int64_t stride_soft, const int8_t* soft, int64_t stride_bits,
+                   const uint8_t* bits, int64_t stride_data, uint8_t* data, int32_t* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,7 +56,12 @@ class IqSegment(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-_vp, _i32, _i64, _f32, _f64, _u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32
+class FecCrc(C.Structure):
+    """sy11_fec_crc: the Rocksoft model of the check sy11_fec_check computes; width 0 = none (include/sy11.h)."""
+    _fields_ = [("width", C.c_int32), ("poly", C.c_uint32), ("init", C.c_uint32), ("xorout", C.c_uint32), ("refin", C.c_int32), ("refout", C.c_int32)]
+
+
+_vp, _i32, _i64, _f32, _f64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32, C.c_uint64
 _dp = C.POINTER(ConvDesc)
 _bp = C.POINTER(BnTail)
 _op = C.POINTER(OptDesc)
@@ -134,6 +139,9 @@ SIGNATURES = {
     "sy11_sync_correlate": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_sync_peaks": [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp],
     "sy11_sync_frames": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "sy11_fec_soft": [_i32, _vp, _vp, _i32, _u64, _i64, _vp, _i64, _i64, _vp, _vp],
+    "sy11_fec_viterbi": [_i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
+    "sy11_fec_check": [_i32, _vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(FecCrc), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],
@@ -158,6 +166,7 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_iq_cyclo_group": ([], C.c_int32),
          "sy11_iq_demod_tile": ([], C.c_int32),
          "sy11_sync_tile": ([], C.c_int32),
+         "sy11_fec_tmax": ([], C.c_int32),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}
 
 _lib = None

@@ -374,6 +374,12 @@ class YOLO:
         from ..data.frames import find_frames
         return find_frames(demodulation, words, payload=payload, threshold=threshold, max_errors=max_errors, t0=t0)
 
+    def decode(self, frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
+        """Decode every frame of ``frames`` (found in ``demodulation``) on the GPU -> ``sy11.data.decode.Decoded``: per frame the Viterbi-decoded, de-whitened
+        information bits, the channel bit errors against the re-encoded decision and whether the CRC holds (``DetectionPredictor.decode``)."""
+        from ..data.decode import decode_frames
+        return decode_frames(frames, demodulation, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

@@ -320,6 +320,21 @@ class DetectionPredictor:
         from ..data.frames import find_frames
         return find_frames(demodulation, words, payload=payload, threshold=threshold, max_errors=max_errors, t0=t0)
 
+    def decode(self, frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
+        """Turn the channel bits of every frame of ``frames`` (what ``find_frames`` returned for ``demodulation``) into a checked message ->
+        ``sy11.data.decode.Decoded``, one row per frame in the frames' order (``csrc/fec.hip``).  The frames are coded with the rate 1/2, K = 7
+        convolutional code of the generators ``polys``, ``n_info`` information bits (the check field included) followed by six zero bits when ``tail``,
+        punctured by the 0/1 pattern ``puncture`` (1 = sent), whitened by the 0/1 sequence ``whiten`` (``sy11.data.decode.lfsr_bits``) and protected by
+        ``crc`` (a name of ``sy11.data.decode.CRCS`` or a Rocksoft dict).  All frames go through THREE launches: the payload symbols turned back by
+        the frame's rotation, scaled so that a clean component is ``soft_scale``, quantised to int8 and depunctured; the Viterbi decoder, one
+        wavefront per frame and one lane per state, in exact integer arithmetic; and the decision encoded again and compared with the
+        received signs (``channel_errors`` of ``n_channel``, ``ber``), the information bits de-whitened and packed on the device (``Decoded.bits(k)``,
+        ``message(k)``) and their CRC (``crc_ok``).  ``find_frames`` must have read ``payload`` symbols enough for the code; a frame cut short by the
+        clip's end is a row with ``valid`` False and the reason "short", one of a clip without a positive gain has the reason "gain".
+        Argument errors are ``ValueError``s raised before anything touches the device; without a valid frame nothing is launched."""
+        from ..data.decode import decode_frames
+        return decode_frames(frames, demodulation, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

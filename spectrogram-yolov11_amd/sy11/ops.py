@@ -1189,6 +1189,170 @@ def sync_frames(sym, frames, words, rows, bits):
     return rows, bits
 
 
+def _fec_table(what, name, t, dtype, dev, n_rows=None, width=None, lo=1, hi=None, even=False):
+    """A contiguous (rows, stride) device table of ``dtype``; ``width``: the exact stride, else ``lo <= stride <= hi``."""
+    bad = t.dtype != dtype or t.dim() != 2 or t.shape[0] == 0 or t.shape[0] >= 2 ** 31 or not t.is_contiguous() or t.device != dev \
+        or (n_rows is not None and t.shape[0] != n_rows)
+    if not bad:
+        s = t.shape[1]
+        bad = s != width if width is not None else (s < lo or s > hi or (even and s % 2 == 1))
+    if bad or t.data_ptr() % {torch.int32: 4, torch.int8: 2, torch.uint8: 1}[dtype]:
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty contiguous (rows, stride) {dtype} tensor on the other tensors' device" +
+                             (f", stride {width}" if width is not None else f", {'an even ' if even else ''}stride in [{lo}, {hi}]") +
+                             ("" if n_rows is None else f", of {n_rows} rows"))
+
+
+def _fec_frames(what, frames, n_rows):
+    """The checks the three launches of the frame decoder share (the library repeats them) -> the contiguous ``FECFRAME`` table."""
+    from .data.decode import FECFRAME, K
+    fr = np.ascontiguousarray(frames)
+    if fr.dtype != FECFRAME or fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `frames` must be a non-empty 1-D array of sy11.data.decode.FECFRAME records")
+    T_MAX = _lib.load().sy11_fec_tmax()
+    T, order, q, tail, row = (fr[k].astype(np.int64) for k in ("T", "order", "q", "tail", "row"))
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: order {int(order[k])} is not 2 or 4")
+    bad = (q < 0) | (q >= order)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: rotation {int(q[k])} is not below the order {int(order[k])}")
+    bad = (tail != 0) & (tail != 1)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: tail {int(tail[k])} is not 0 or 1")
+    bad = (T < np.where(tail == 1, K, 1)) | (T > T_MAX)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: {int(T[k])} trellis steps are not {K if tail[k] else 1} .. {T_MAX}")
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        k = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise _lib.Sy11Error(f"{what}: frame {k} writes row {int(row[k])} of a table of {n_rows} rows (a row takes one frame)")
+    return fr
+
+
+def _fec_polys(what, polys):
+    try:
+        g = tuple(polys)
+    except TypeError:
+        g = ()
+    if len(g) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v < 128 and (v & 0x41) == 0x41 for v in g):
+        raise _lib.Sy11Error(f"{what}: the generators {polys!r} are not two 7-bit integers with bits 6 and 0 set")
+    return int(g[0]), int(g[1])
+
+
+def _fec_fit(what, fr, stride_soft, stride_bits=None):
+    bad = 2 * fr["T"].astype(np.int64) > stride_soft
+    if stride_bits is not None:
+        bad |= (fr["T"].astype(np.int64) + 7) // 8 > stride_bits
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: {int(fr['T'][k])} steps leave a row of {stride_soft} soft bytes" + ("" if stride_bits is None else f" or {stride_bits} bit bytes"))
+
+
+def fec_soft(sym, frames, soft, period=2, pattern=3):
+    """Launch 1 of the frame decoder (sy11_fec_soft): every frame of ``frames`` — ``sy11.data.decode.FECFRAME`` records (sym_off, T, order, q, tail, row, scale):
+    the payload symbols from ``sym[sym_off]`` on, turned back by ``q`` steps of 2 pi / order — writes its ``2T`` depunctured soft bits
+    ``clamp(rintf(x * scale), -127, 127)`` to ``soft[row]`` (rows, stride) int8, 0 where the puncture pattern (bit i of ``pattern`` = mother position i, applied with the
+    even ``period`` <= 64; 1 = sent) removed the bit.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``soft``."""
+    what = "fec_soft"
+    _need_gpu(sym, soft)
+    _packed_c64(what, "sym", sym)
+    T_MAX = _lib.load().sy11_fec_tmax()
+    _fec_table(what, "soft", soft, torch.int8, sym.device, lo=2, hi=2 * T_MAX, even=True)
+    fr = _fec_frames(what, frames, soft.shape[0])
+    if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or not 2 <= period <= 64 or period % 2 or isinstance(pattern, bool) \
+            or not isinstance(pattern, (int, np.integer)) or not 0 < pattern < 2 ** int(period):
+        raise _lib.Sy11Error(f"{what}: the pattern {pattern!r} of period {period!r} is not a non-zero word of an even 2 .. 64 positions")
+    period, pattern = int(period), int(pattern)
+    _fec_fit(what, fr, soft.shape[1])
+    pat = np.array([(pattern >> i) & 1 for i in range(period)], dtype=np.int64)
+    twoT = 2 * fr["T"].astype(np.int64)
+    n_coded = twoT // period * int(pat.sum()) + np.concatenate(([0], np.cumsum(pat)))[twoT % period]
+    w = fr["order"].astype(np.int64) // 2
+    need = -(-n_coded // w)
+    bad = (fr["sym_off"] < 0) | (fr["sym_off"] > sym.shape[0] - need)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: the {int(need[k])} payload symbols at {int(fr['sym_off'][k])} leave the {sym.shape[0]} packed symbols")
+    bad = ~(np.isfinite(fr["scale"]) & (fr["scale"] > 0))
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: the scale {float(fr['scale'][k])!r} is not finite and above 0")
+    t = torch.from_numpy(fr.view(np.uint8)).to(sym.device)
+    call("sy11_fec_soft", fr.shape[0], C.c_void_p(fr.ctypes.data), C.c_void_p(t.data_ptr()), period, pattern, sym.shape[0],
+         C.c_void_p(torch.view_as_real(sym).data_ptr()), soft.shape[0], soft.shape[1], _p(soft), _stream())
+    t.record_stream(torch.cuda.current_stream(sym.device))
+    return soft
+
+
+def fec_viterbi(soft, frames, polys, bits, out):
+    """Launch 2 of the frame decoder (sy11_fec_viterbi): the Viterbi decoder of the rate 1/2, K = 7 code with the generators ``polys`` over the ``2T`` soft bits
+    ``soft[row]`` of every frame of ``frames`` (int32 path metrics from state 0; traceback from state 0 with ``tail``, else from the best state, the lowest on
+    a tie) — writes the ``T`` decided bits packed MSB first, zero-padded, to ``bits[row]`` (rows, stride) uint8 and (final metric, end state) to ``out[row]``
+    (rows, 2) int32.  One wavefront per frame.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``(bits, out)``."""
+    what = "fec_viterbi"
+    _need_gpu(soft, bits, out)
+    T_MAX = _lib.load().sy11_fec_tmax()
+    _fec_table(what, "soft", soft, torch.int8, soft.device, lo=2, hi=2 * T_MAX, even=True)
+    _fec_table(what, "bits", bits, torch.uint8, soft.device, n_rows=soft.shape[0], lo=1, hi=T_MAX // 8)
+    _fec_table(what, "out", out, torch.int32, soft.device, n_rows=soft.shape[0], width=2)
+    g0, g1 = _fec_polys(what, polys)
+    fr = _fec_frames(what, frames, soft.shape[0])
+    _fec_fit(what, fr, soft.shape[1], bits.shape[1])
+    t = torch.from_numpy(fr.view(np.uint8)).to(soft.device)
+    call("sy11_fec_viterbi", fr.shape[0], C.c_void_p(fr.ctypes.data), C.c_void_p(t.data_ptr()), g0, g1, soft.shape[0], soft.shape[1], _p(soft), bits.shape[1], _p(bits),
+         _p(out), _stream())
+    t.record_stream(torch.cuda.current_stream(soft.device))
+    return bits, out
+
+
+def fec_check(soft, bits, frames, polys, n_info, data, rows, whiten=None, crc=None):
+    """Launch 3 of the frame decoder (sy11_fec_check): for every frame of ``frames`` the decided bits ``bits[row]`` are encoded again and compared with the signs
+    of ``soft[row]`` where it is not 0; the first ``n_info`` of them, XORed with ``whiten`` (a uint8 device vector of ``n_info`` 0/1, or None), are written packed MSB first,
+    zero-padded, to ``data[row]`` (rows, stride) uint8, and (crc_calc, crc_recv, crc_ok, channel_errors, n_channel) to ``rows[row]`` (rows, 5) int32; ``crc``: None
+    (crc_ok = -1) or a dict width / poly / init / refin / refout / xorout (``sy11.data.decode.CRCS``).  A refused call raises ``Sy11Error`` and writes nothing.
+    -> ``(data, rows)``."""
+    from .data.decode import K
+    what = "fec_check"
+    _need_gpu(soft, bits, data, rows)
+    T_MAX = _lib.load().sy11_fec_tmax()
+    dev, n = soft.device, soft.shape[0]
+    _fec_table(what, "soft", soft, torch.int8, dev, lo=2, hi=2 * T_MAX)
+    _fec_table(what, "bits", bits, torch.uint8, dev, n_rows=n, lo=1, hi=T_MAX // 8)
+    _fec_table(what, "data", data, torch.uint8, dev, n_rows=n, lo=1, hi=T_MAX // 8)
+    _fec_table(what, "rows", rows, torch.int32, dev, n_rows=n, width=5)
+    g0, g1 = _fec_polys(what, polys)
+    if isinstance(n_info, bool) or not isinstance(n_info, (int, np.integer)) or not 1 <= n_info <= T_MAX or (n_info + 7) // 8 > data.shape[1]:
+        raise _lib.Sy11Error(f"{what}: {n_info!r} information bits are not 1 .. {T_MAX} or leave the {data.shape[1]} bytes of a data row")
+    n_info = int(n_info)
+    if whiten is not None:
+        _u8_vector(what, "whiten", whiten, dev, n_info)
+    spec = _lib.FecCrc()
+    if crc is not None:
+        try:
+            W, poly, init, xorout, refin, refout = (int(crc[k]) for k in ("width", "poly", "init", "xorout", "refin", "refout"))
+        except (KeyError, TypeError, ValueError):
+            raise _lib.Sy11Error(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
+        if not 8 <= W <= 32 or n_info <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) or refout not in (0, 1) \
+                or (refin and (n_info - W) % 8):
+            raise _lib.Sy11Error(f"{what}: the crc {crc!r} is not of 8 .. 32 bits below n_info = {n_info}, with fields of that width (and whole bytes with refin)")
+        spec = _lib.FecCrc(W, poly, init, xorout, refin, refout)
+    fr = _fec_frames(what, frames, n)
+    bad = fr["T"].astype(np.int64) != n_info + (K - 1) * fr["tail"].astype(np.int64)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: frame {k}: {int(fr['T'][k])} steps are not the {n_info} information bits" + (" and a tail of 6" if fr["tail"][k] else ""))
+    _fec_fit(what, fr, soft.shape[1], bits.shape[1])
+    t = torch.from_numpy(fr.view(np.uint8)).to(dev)
+    call("sy11_fec_check", fr.shape[0], C.c_void_p(fr.ctypes.data), C.c_void_p(t.data_ptr()), g0, g1, n_info, _p(whiten), C.byref(spec), n, soft.shape[1], _p(soft),
+         bits.shape[1], _p(bits), data.shape[1], _p(data), _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return data, rows
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
