@@ -69,6 +69,10 @@ const char* sy11_last_error(void);
  * launches, not concurrently with them.                                                                                */
 int sy11_set_option(const char* name, int32_t value);
 int sy11_get_option(const char* name, int32_t* value);
+/* Two more names are READ-ONLY (sy11_get_option answers, sy11_set_option fails with a message): igemm_last_cfg and wgrad_last_cfg,
+ * the tile configuration of the most recent forward / input-gradient launch and of the most recent filter-gradient launch
+ * (csrc/igemm.hip 0..25, csrc/wgrad.hip 0..19; 100 = the fused-parity stride-2 input gradient, which is no entry of the igemm
+ * table; -1 before the first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.       */
 /* The autotuner's pick tables as a flat array of 16-byte records {u64 problem hash, i32 kind, i32 pick}: export on one
  * rank, broadcast, import on the others, so every rank of a data-parallel job (engine/trainer.py:217-228) runs the same
  * kernels.  sy11_tune_export returns the number of bytes needed (pass buf = NULL to size the buffer).                 */

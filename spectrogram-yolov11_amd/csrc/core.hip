@@ -37,6 +37,16 @@ int sy11_opt(int which) {
   std::call_once(g_opt_once, opt_init);
   return g_opt[which];
 }
+// last launched configuration per table (tune.h): plain ints, written by the launching thread
+static int g_last_cfg[2] = {-1, -1};
+static const char* const kLastCfgName[2] = {"igemm_last_cfg", "wgrad_last_cfg"};
+void sy11_note_cfg(int kind, int cfg) { g_last_cfg[kind] = cfg; }
+static int last_cfg_index(const char* name) {
+  if (name)
+    for (int i = 0; i < 2; ++i)
+      if (!strcmp(name, kLastCfgName[i])) return i;
+  return -1;
+}
 static int opt_index(const char* name) {
   if (name)
     for (int i = 0; i < OPT_COUNT; ++i)
@@ -45,13 +55,15 @@ static int opt_index(const char* name) {
 }
 extern "C" int sy11_set_option(const char* name, int32_t value) {
   const int i = opt_index(name);
-  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic)", name ? name : "(null)");
+  SY11_REQUIRE(last_cfg_index(name) < 0, "set_option: '%s' is read-only (the configuration of the last launch)", name);
+  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic; read-only: igemm_last_cfg, wgrad_last_cfg)", name ? name : "(null)");
   std::call_once(g_opt_once, opt_init);
   g_opt[i] = value;
   return SY11_OK;
 }
 extern "C" int sy11_get_option(const char* name, int32_t* value) {
   const int i = opt_index(name);
+  if (value && last_cfg_index(name) >= 0) { *value = g_last_cfg[last_cfg_index(name)]; return SY11_OK; }
   SY11_REQUIRE(i >= 0 && value, "get_option: unknown option '%s' or null result pointer", name ? name : "(null)");
   *value = sy11_opt(i);
   return SY11_OK;

@@ -577,6 +577,7 @@ static bool cfg_legal(const IgemmArgs& a, int cfg) {
 
 template <typename T>
 static int launch_cfg(IgemmArgs a, hipStream_t st, int cfg) {
+  sy11_note_cfg(0, cfg);
   if (cfg >= 15 && cfg <= 18) return sy11_halo3x3_launch(a, halo_bn(a, cfg), st);
   if (cfg == 19) return sy11_smallc3x3_launch(a, ElemTraits<T>::code, st);
   if (cfg == 7 || cfg == 8)
@@ -890,7 +891,7 @@ extern "C" int sy11_conv2d_dgrad(const sy11_conv_desc* d, const void* dy, int32_
     const long xb = (((long)d->B * d->OH * d->OW - 1) * dy_ld + d->N) * 2, wb = (long)d->C * 9 * d->N * 2;
     if (xb < (1L << 31) && wb < (1L << 31)) {
       a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-      if (sy11_halo_dgrad_s2_legal(a)) return sy11_halo_dgrad_s2_launch(a, st);
+      if (sy11_halo_dgrad_s2_legal(a)) { sy11_note_cfg(0, SY11_CFG_HALO_DGRAD_S2); return sy11_halo_dgrad_s2_launch(a, st); }
     }
   }
   // one launch per output-parity class (ph, pw): pixels i = SH*i' + ph use only taps with (ph + PH - r*DH) % SH == 0

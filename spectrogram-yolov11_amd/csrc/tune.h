@@ -23,6 +23,11 @@ constexpr int SY11_WGRAD_NCFG = 20;
 // SY11_WGRAD_CFG, SY11_IGEMM_KORDER, SY11_IGEMM_DEEP, SY11_IGEMM_BPOL), sy11_set_option() changes them at run time
 enum Sy11Opt { OPT_TUNE = 0, OPT_TUNE_LOG, OPT_IGEMM_CFG, OPT_WGRAD_CFG, OPT_IGEMM_KORDER, OPT_IGEMM_DEEP, OPT_IGEMM_BPOL, OPT_DGRAD_S2_HALO, OPT_ROW_MAP, OPT_DETERMINISTIC, OPT_COUNT };
 int sy11_opt(int which);
+// the configuration of the most recent launch of each table (core.hip), read-only through sy11_get_option as "igemm_last_cfg" /
+// "wgrad_last_cfg"; -1 before the first launch.  One host-side int store per launch: tests read back which kernel they checked.
+// The fused-parity stride-2 input gradient (conv3x3.hip halo_dgrad_s2_kernel) is no entry of the igemm table: it records this value.
+constexpr int SY11_CFG_HALO_DGRAD_S2 = 100;
+void sy11_note_cfg(int kind, int cfg);      // kind 0 = igemm (fwd / dgrad), 1 = wgrad
 
 namespace sy11tune {
 

@@ -751,6 +751,7 @@ constexpr int WGRAD_NCFG = SY11_WGRAD_NCFG;
 static_assert(WGRAD_NCFG == 20, "configuration table and its size (tune.h) out of step");
 constexpr int WGRAD_WIDE_LDS = 2 * 64 * ((128 * 2 + 64) + (256 * 2 + 64));
 static int wgrad_launch_cfg(WgradArgs a, int dtype, hipStream_t st, int cfg) {
+  sy11_note_cfg(1, cfg);
   const int kind = cfg >> 2;
   const bool psplit = kind == 2;
   const bool patch = kind == 3;

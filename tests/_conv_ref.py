@@ -135,8 +135,10 @@ REAL_DENSE_CASES = [(2, 32, 48, 11, 13, 5, 1, 2, 1), (2, 64, 64, 15, 17, 3, 2, 2
 
 
 # ------------------------------------------------------------------------------------------------------------ operands
-def int_operands(B, C, N, H, W, k, s, p, d, g, seed=SEED):
-    """Integer operands of the exact family as float64 NCHW / OIHW tensors: (x, w, dy)."""
+def int_operands(B, C, N, H, W, k, s, p, d, g, seed=SEED, density=None):
+    """Integer operands of the exact family as float64 NCHW / OIHW tensors: (x, w, dy).  `density` (None: every value of the range
+    equally likely, as before) is the fraction of non-zeros of each operand, drawn after the values so that the default is unchanged:
+    long sums (K or 9 N in the thousands) stay inside the exact range without losing the -1 / 0 / 1 alphabet."""
     kh, kw = pair(k)
     OH, OW = out_hw(H, W, k, s, p, d)
     depthwise = g == C and C == N
@@ -145,6 +147,12 @@ def int_operands(B, C, N, H, W, k, s, p, d, g, seed=SEED):
     x = torch.randint(-ax, ax + 1, (B, C, H, W), generator=gen).double()
     w = torch.randint(-aw, aw + 1, (N, C // g, kh, kw), generator=gen).double()
     dy = torch.randint(-ax, ax + 1, (B, N, OH, OW), generator=gen).double()
+    if density is not None:
+        def sparse(t, a):
+            sign = torch.randint(0, 2, t.shape, generator=gen).double() * 2 - 1
+            mag = torch.randint(1, a + 1, t.shape, generator=gen).double()
+            return sign * mag * (torch.rand(t.shape, generator=gen) < density)
+        x, w, dy = sparse(x, ax), sparse(w, aw), sparse(dy, ax)
     return x, w, dy
 
 
@@ -219,10 +227,10 @@ def assert_exact_conditions(x, dy, y, dx, dw):
 
 
 @functools.lru_cache(maxsize=3)
-def exact_case(B, C, N, H, W, k, s, p, d, g, seed=SEED):
+def exact_case(B, C, N, H, W, k, s, p, d, g, seed=SEED, density=None):
     """Operands and float64 results of an exact case, computed once and shared (callers must not write into them):
     dict with x, w, dy, y, dx, dw (NCHW / OIHW) after `assert_exact_conditions`."""
-    x, w, dy = int_operands(B, C, N, H, W, k, s, p, d, g, seed)
+    x, w, dy = int_operands(B, C, N, H, W, k, s, p, d, g, seed, density)
     y, dx, dw = conv_ref(x, w, dy, s, p, d, g)
     assert_exact_conditions(x, dy, y, dx, dw)
     return {"x": x, "w": w, "dy": dy, "y": y, "dx": dx, "dw": dw}

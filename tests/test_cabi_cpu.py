@@ -71,6 +71,13 @@ def test_run_time_options_round_trip_and_reject_unknown_names():
         finally:
             _lib.set_option(n, old)
     assert lib.sy11_set_option(b"no_such_option", 1) == -1 and b"unknown option" in lib.sy11_last_error()
+    # the configuration of the last launch: readable, -1 in a library that has launched nothing (always so without a GPU; in one
+    # process with the GPU tests an earlier conv may have left its configuration), refused on set
+    import torch
+    for n in ("igemm_last_cfg", "wgrad_last_cfg"):
+        before = _lib.get_option(n)
+        assert n in HEADER and (-1 <= before <= 100 if torch.cuda.is_available() else before == -1)
+        assert lib.sy11_set_option(n.encode(), 3) == -1 and b"read-only" in lib.sy11_last_error() and _lib.get_option(n) == before
 
 
 def test_product_fails_loudly_on_cpu_tensors():

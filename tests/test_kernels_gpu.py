@@ -167,6 +167,7 @@ def test_every_igemm_and_wgrad_tile_configuration(case):
     ref_dx = torch.nn.grad.conv2d_input((B, Cn, H, W), wq, dyq, s, p)
     ref_dw = torch.nn.grad.conv2d_weight(xq, (N, Cn, k, k), dyq, s, p)
     tune0 = _lib.get_option("tune")
+    ran_fwd, ran_dgrad, ran_wgrad = set(), set(), set()
     try:
         _lib.set_option("tune", 0)
         for cfg in range(26):
@@ -176,8 +177,10 @@ def test_every_igemm_and_wgrad_tile_configuration(case):
             o.conv2d_fwd(xv, wk, y, k, s, p, stats=(ssum, ssq))
             close(to_nchw(y), ref, dtype, f"fwd cfg {cfg}")
             close(ssum.cpu(), ref.sum((0, 2, 3)), dtype, f"stats cfg {cfg}", mult=4 * math.sqrt(B * OH * OW))
+            ran_fwd.add(_lib.get_option("igemm_last_cfg"))
             dx = torch.zeros(B, H, W, Cn, dtype=dtype, device=DEV)
             o.conv2d_dgrad(dyv, wt, dx, (B, OH, OW, N), k, s, p, accumulate=(s > 1))
+            ran_dgrad.add(_lib.get_option("igemm_last_cfg"))
             close(to_nchw(dx), ref_dx, dtype, f"dgrad cfg {cfg}")
             o.conv2d_dgrad(dyv, wt, dx, (B, OH, OW, N), k, s, p, accumulate=True)
             close(to_nchw(dx), 2 * ref_dx, dtype, f"dgrad accumulate cfg {cfg}", mult=2)
@@ -186,7 +189,11 @@ def test_every_igemm_and_wgrad_tile_configuration(case):
             _lib.set_option("wgrad_cfg", cfg)
             dw = torch.zeros(N, k, k, Cn, dtype=torch.float32, device=DEV)
             o.conv2d_wgrad(xv, dyv, dw, k, s, p)
+            ran_wgrad.add(_lib.get_option("wgrad_last_cfg"))
             close(dw.cpu().permute(0, 3, 1, 2), ref_dw, torch.float32, f"wgrad cfg {cfg}", mult=8)
+        # how many of the forced configurations really ran (the others fell back to the heuristic pick); run with -s to see it
+        print(f"\nCFG_CASE {case}: forward ran {len(ran_fwd)} of 26 configurations {sorted(ran_fwd)}, input gradient (last launch) "
+              f"{len(ran_dgrad)} of 26 {sorted(ran_dgrad)}, filter gradient {len(ran_wgrad)} of 20 {sorted(ran_wgrad)}")
     finally:
         _lib.set_option("igemm_cfg", -1)
         _lib.set_option("wgrad_cfg", -1)
