@@ -72,7 +72,10 @@ int sy11_get_option(const char* name, int32_t* value);
 /* Two more names are READ-ONLY (sy11_get_option answers, sy11_set_option fails with a message): igemm_last_cfg and wgrad_last_cfg,
  * the tile configuration of the most recent forward / input-gradient launch and of the most recent filter-gradient launch
  * (csrc/igemm.hip 0..25, csrc/wgrad.hip 0..19; 100 = the fused-parity stride-2 input gradient, which is no entry of the igemm
- * table; -1 before the first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.       */
+ * table; -1 before the first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.
+ * Likewise stem_fwd_last and stem_wgrad_last: which first-layer kernel (csrc/direct.hip) the most recent sy11_stem_conv_fwd[_bn] /
+ * sy11_stem_conv_wgrad launched — 1 gather, 2 MFMA gather, 3 LDS-tiled with 16-byte image loads, 4 LDS-tiled with element-wise
+ * fill; -1 before the first launch.                                                                                          */
 /* The autotuner's pick tables as a flat array of 16-byte records {u64 problem hash, i32 kind, i32 pick}: export on one
  * rank, broadcast, import on the others, so every rank of a data-parallel job (engine/trainer.py:217-228) runs the same
  * kernels.  sy11_tune_export returns the number of bytes needed (pass buf = NULL to size the buffer).                 */
@@ -142,7 +145,9 @@ int sy11_weight_transpose(int32_t dtype, int32_t N, int32_t T, int32_t C, const 
 int sy11_weight_transpose_multi(int32_t dtype, int32_t nlayers, int32_t total_tiles, const void* desc, const void* src,
                                 void* dst, void* stream);
 
-/* first layer: x is the caller's NCHW f32 image (B,3,H,W) in [0,1] (detect/train.py:59 output); y NHWC.    */
+/* first layer: x is the caller's NCHW f32 image (B,3,H,W) in [0,1] (detect/train.py:59 output); y NHWC.
+ * stat_sum / stat_sq receive the per-channel sum and sum of squares of the RAW convolution — the f32 accumulator before bias,
+ * activation and the rounding to the output type — in every kernel behind these entry points (what BatchNorm normalises).   */
 int sy11_stem_conv_fwd(const sy11_conv_desc* d, const float* x_nchw, const void* w, const float* bias, void* y,
                        float* stat_sum, float* stat_sq, void* stream);
 int sy11_stem_conv_fwd_bn(const sy11_conv_desc* d, const float* x_nchw, const void* w, void* y, float* stat_sum,

@@ -38,12 +38,12 @@ int sy11_opt(int which) {
   return g_opt[which];
 }
 // last launched configuration per table (tune.h): plain ints, written by the launching thread
-static int g_last_cfg[2] = {-1, -1};
-static const char* const kLastCfgName[2] = {"igemm_last_cfg", "wgrad_last_cfg"};
+static int g_last_cfg[4] = {-1, -1, -1, -1};
+static const char* const kLastCfgName[4] = {"igemm_last_cfg", "wgrad_last_cfg", "stem_fwd_last", "stem_wgrad_last"};
 void sy11_note_cfg(int kind, int cfg) { g_last_cfg[kind] = cfg; }
 static int last_cfg_index(const char* name) {
   if (name)
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 4; ++i)
       if (!strcmp(name, kLastCfgName[i])) return i;
   return -1;
 }
@@ -56,7 +56,7 @@ static int opt_index(const char* name) {
 extern "C" int sy11_set_option(const char* name, int32_t value) {
   const int i = opt_index(name);
   SY11_REQUIRE(last_cfg_index(name) < 0, "set_option: '%s' is read-only (the configuration of the last launch)", name);
-  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic; read-only: igemm_last_cfg, wgrad_last_cfg)", name ? name : "(null)");
+  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic; read-only: igemm_last_cfg, wgrad_last_cfg, stem_fwd_last, stem_wgrad_last)", name ? name : "(null)");
   std::call_once(g_opt_once, opt_init);
   g_opt[i] = value;
   return SY11_OK;

@@ -827,6 +827,10 @@ typedef short as16x4_t __attribute__((ext_vector_type(4)));
 // packs them to 16 bit and feeds v_mfma_f32_32x32x16; the filter sits in registers as the B operand.  The accumulator
 // tile has col = output channel (lane), rows = pixels (registers): BN statistics are in-lane sums + one shuffle, and
 // the tile is transposed through LDS so that the NHWC output leaves in 16-byte coalesced stores.
+// PADDING 0 OR 1 ONLY (the host, stem_fwd_tail, sends nothing else): a tap's offsets r - PH and s - PW are kept as
+// (offset + 1) in two bits each, and masked slots load from the pixel origin (oy * SH, ox * SW) unclamped, which lies inside the
+// image only while OH and OW come from padding <= 1.  More padding decodes other taps and reads past the image; such shapes take
+// stem_fwd_kernel.  stem_wgrad_mma keeps its tap offset unpacked and clamps every coordinate: it takes any padding.
 typedef short ss16x8 __attribute__((ext_vector_type(8)));
 template <typename T> struct StemMma;
 template <> struct StemMma<_Float16> {
@@ -1430,7 +1434,7 @@ static int stem_fwd_tail(const sy11_conv_desc* d, const float* x_nchw, const voi
   const long M = (long)d->B * d->OH * d->OW;
   dim3 grid((unsigned)((M + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  const bool mma = d->dtype != SY11_F32 && (d->N == 32 || d->N == 64) && d->y_ld == d->N && ((uintptr_t)y & 15) == 0 &&
+  bool mma = d->dtype != SY11_F32 && (d->N == 32 || d->N == 64) && d->y_ld == d->N && ((uintptr_t)y & 15) == 0 &&
                    (long)d->B * 3 * d->IH * d->IW < (1L << 31) && (long)(d->OW + 64) * d->OW < (1L << 20) && (long)(d->OH + 64) * d->OH < (1L << 20);
   static int tile_env = -1, tile_wg = 0;
   if (tile_env < 0) {
@@ -1439,6 +1443,9 @@ static int stem_fwd_tail(const sy11_conv_desc* d, const float* x_nchw, const voi
   }
   StemTiling tg{};
   const bool tiled = mma && tile_env && stem_tiling(d, &tg);
+  // stem_fwd_mma packs a tap's row / column offset into two bits each and loads from the unclamped pixel origin: both hold for
+  // padding 0 and 1 only, so a non-tiled shape with more padding goes to the general kernel
+  if (mma && !tiled && (d->PH > 1 || d->PW > 1)) mma = false;
   if (tiled) grid = dim3((unsigned)(tg.tiles < tile_wg ? tg.tiles : tile_wg));
   DetPartials dp;                                             // ordered mode (det.h): one partial statistics row per workgroup
   const bool det = stat_sum && sy11_det(2) && !tail.ticket;
@@ -1455,12 +1462,14 @@ static int stem_fwd_tail(const sy11_conv_desc* d, const float* x_nchw, const voi
         const bool vec = (d->IW & 3) == 0 && ((uintptr_t)x_nchw & 15) == 0;
         if (d->N == 32) { if (vec) hipLaunchKernelGGL((stem_fwd_tile<T, 1, true>), grid, block, 0, st, a, tail, tg); else hipLaunchKernelGGL((stem_fwd_tile<T, 1, false>), grid, block, 0, st, a, tail, tg); }
         else { if (vec) hipLaunchKernelGGL((stem_fwd_tile<T, 2, true>), grid, block, 0, st, a, tail, tg); else hipLaunchKernelGGL((stem_fwd_tile<T, 2, false>), grid, block, 0, st, a, tail, tg); }
+        sy11_note_cfg(2, vec ? SY11_STEM_TILE_VEC : SY11_STEM_TILE_SCALAR);
       });
     } else {
       SY11_DISPATCH_DTYPE(d->dtype, T, {
         if (d->N == 32) hipLaunchKernelGGL((stem_fwd_mma<T, 1>), grid, block, 0, st, a, tail);
         else hipLaunchKernelGGL((stem_fwd_mma<T, 2>), grid, block, 0, st, a, tail);
       });
+      sy11_note_cfg(2, SY11_STEM_MMA);
     }
     SY11_LAUNCH_CHECK("stem_conv_fwd");
     *tail_done = tail.ticket != nullptr && stat_sum != nullptr;
@@ -1469,6 +1478,7 @@ static int stem_fwd_tail(const sy11_conv_desc* d, const float* x_nchw, const voi
   if (d->N <= 16) { SY11_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL((stem_fwd_kernel<T, 16>), grid, block, 0, st, a)); }
   else if (d->N <= 32) { SY11_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL((stem_fwd_kernel<T, 32>), grid, block, 0, st, a)); }
   else { SY11_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL((stem_fwd_kernel<T, 64>), grid, block, 0, st, a)); }
+  sy11_note_cfg(2, SY11_STEM_GATHER);
   SY11_LAUNCH_CHECK("stem_conv_fwd");
   return det ? det_end() : SY11_OK;
 }
@@ -1521,12 +1531,14 @@ extern "C" int sy11_stem_conv_wgrad(const sy11_conv_desc* d, const float* x_nchw
         const bool vec = (d->IW & 3) == 0 && ((uintptr_t)x_nchw & 15) == 0;
         if (d->N == 32) { if (vec) hipLaunchKernelGGL((stem_wgrad_tile<T, 1, true>), gm, block, 0, st, am, dwk, pstride, tg); else hipLaunchKernelGGL((stem_wgrad_tile<T, 1, false>), gm, block, 0, st, am, dwk, pstride, tg); }
         else { if (vec) hipLaunchKernelGGL((stem_wgrad_tile<T, 2, true>), gm, block, 0, st, am, dwk, pstride, tg); else hipLaunchKernelGGL((stem_wgrad_tile<T, 2, false>), gm, block, 0, st, am, dwk, pstride, tg); }
+        sy11_note_cfg(3, vec ? SY11_STEM_TILE_VEC : SY11_STEM_TILE_SCALAR);
       });
     } else {
       SY11_DISPATCH_DTYPE(d->dtype, T, {
         if (d->N == 32) hipLaunchKernelGGL((stem_wgrad_mma<T, 1>), gm, block, 0, st, am, dwk, ppbm, pstride);
         else hipLaunchKernelGGL((stem_wgrad_mma<T, 2>), gm, block, 0, st, am, dwk, ppbm, pstride);
       });
+      sy11_note_cfg(3, SY11_STEM_MMA);
     }
     SY11_LAUNCH_CHECK("stem_conv_wgrad");
     return dp.base ? dp.fold(0, dw) : SY11_OK;
@@ -1541,6 +1553,7 @@ extern "C" int sy11_stem_conv_wgrad(const sy11_conv_desc* d, const float* x_nchw
   if (d->N <= 16) { SY11_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL((stem_wgrad_kernel<T, 16>), grid, block, 0, st, a, dy_ld, dwk, ppb, pstride)); }
   else if (d->N <= 32) { SY11_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL((stem_wgrad_kernel<T, 32>), grid, block, 0, st, a, dy_ld, dwk, ppb, pstride)); }
   else { SY11_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL((stem_wgrad_kernel<T, 64>), grid, block, 0, st, a, dy_ld, dwk, ppb, pstride)); }
+  sy11_note_cfg(3, SY11_STEM_GATHER);
   SY11_LAUNCH_CHECK("stem_conv_wgrad");
   return dp.base ? dp.fold(0, dw) : SY11_OK;
 }

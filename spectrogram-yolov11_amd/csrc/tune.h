@@ -27,7 +27,13 @@ int sy11_opt(int which);
 // "wgrad_last_cfg"; -1 before the first launch.  One host-side int store per launch: tests read back which kernel they checked.
 // The fused-parity stride-2 input gradient (conv3x3.hip halo_dgrad_s2_kernel) is no entry of the igemm table: it records this value.
 constexpr int SY11_CFG_HALO_DGRAD_S2 = 100;
-void sy11_note_cfg(int kind, int cfg);      // kind 0 = igemm (fwd / dgrad), 1 = wgrad
+void sy11_note_cfg(int kind, int cfg);      // kind 0 = igemm (fwd / dgrad), 1 = wgrad, 2 = stem forward, 3 = stem filter gradient
+// which of the first layer's kernels (direct.hip) the last sy11_stem_conv_fwd[_bn] / sy11_stem_conv_wgrad launched, read-only as
+// "stem_fwd_last" / "stem_wgrad_last" (kinds 2 / 3 of sy11_note_cfg); -1 before the first launch
+constexpr int SY11_STEM_GATHER = 1;         // stem_fwd_kernel / stem_wgrad_kernel: any dtype, N, leading dimension, geometry
+constexpr int SY11_STEM_MMA = 2;            // stem_fwd_mma / stem_wgrad_mma: MFMA, operands gathered from the image
+constexpr int SY11_STEM_TILE_VEC = 3;       // stem_fwd_tile / stem_wgrad_tile, image rows by 16-byte loads
+constexpr int SY11_STEM_TILE_SCALAR = 4;    // stem_fwd_tile / stem_wgrad_tile, image rows element by element
 
 namespace sy11tune {
 

@@ -234,12 +234,14 @@ def call(name: str, *args):
 
 def set_option(name: str, value: int):
     """sy11_set_option: "tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo",
-    "row_map", "deterministic".  "igemm_last_cfg" / "wgrad_last_cfg" are read-only (get_option) and refused here."""
+    "row_map", "deterministic".  "igemm_last_cfg" / "wgrad_last_cfg" / "stem_fwd_last" / "stem_wgrad_last" are read-only
+    (get_option) and refused here."""
     check(load().sy11_set_option(name.encode(), int(value)), "sy11_set_option")
 
 
 def get_option(name: str) -> int:
-    """sy11_get_option: every option of set_option, plus "igemm_last_cfg" / "wgrad_last_cfg" (the configuration of the last launch)."""
+    """sy11_get_option: every option of set_option, plus "igemm_last_cfg" / "wgrad_last_cfg" (the configuration of the last launch)
+    and "stem_fwd_last" / "stem_wgrad_last" (which first-layer kernel the last launch was: 1 gather, 2 MFMA gather, 3 / 4 LDS-tiled)."""
     v = C.c_int32(0)
     check(load().sy11_get_option(name.encode(), C.byref(v)), "sy11_get_option")
     return int(v.value)

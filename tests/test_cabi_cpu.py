@@ -74,9 +74,10 @@ def test_run_time_options_round_trip_and_reject_unknown_names():
     # the configuration of the last launch: readable, -1 in a library that has launched nothing (always so without a GPU; in one
     # process with the GPU tests an earlier conv may have left its configuration), refused on set
     import torch
-    for n in ("igemm_last_cfg", "wgrad_last_cfg"):
+    for n in ("igemm_last_cfg", "wgrad_last_cfg", "stem_fwd_last", "stem_wgrad_last"):
         before = _lib.get_option(n)
-        assert n in HEADER and (-1 <= before <= 100 if torch.cuda.is_available() else before == -1)
+        top = 4 if n.startswith("stem") else 100
+        assert n in HEADER and (-1 <= before <= top if torch.cuda.is_available() else before == -1)
         assert lib.sy11_set_option(n.encode(), 3) == -1 and b"read-only" in lib.sy11_last_error() and _lib.get_option(n) == before
 
 

@@ -432,6 +432,8 @@ def test_stem_conv_lds_tiles(N, B, H, W, s, p, dtype):
     y = torch.full((B, OH, OW, N), float("nan"), dtype=dtype, device=DEV)
     ssum, ssq = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
     o.stem_conv_fwd(x.to(DEV), wk, y, s, p, stats=(ssum, ssq))
+    from sy11 import _lib
+    assert _lib.get_option("stem_fwd_last") == (3 if W % 4 == 0 else 4)      # csrc/tune.h: tiled, 16-byte loads / element-wise fill
     ref = F.conv2d(xq, wq, None, s, p)
     close(to_nchw(y), ref, dtype, "stem fwd")
     close(ssum.cpu(), ref.sum((0, 2, 3)), dtype, "stem sum", mult=4)
@@ -439,6 +441,7 @@ def test_stem_conv_lds_tiles(N, B, H, W, s, p, dtype):
     dy = rnd(B, N, OH, OW, seed=33)
     dw = torch.zeros(N, 3, 3, 3, dtype=torch.float32, device=DEV)
     o.stem_conv_wgrad(x.to(DEV), nhwc(dy, dtype), dw, s, p)
+    assert _lib.get_option("stem_wgrad_last") == (3 if W % 4 == 0 else 4)
     close(dw.cpu().permute(0, 3, 1, 2), torch.nn.grad.conv2d_weight(xq, (N, 3, 3, 3), q(dy, dtype), s, p), torch.float32,
           "stem wgrad", mult=8)
     dw2 = torch.zeros_like(dw)                                 # accumulates, and twice the same
@@ -460,6 +463,9 @@ def test_stem_conv(N, H, W, dtype):
     y = torch.empty(B, OH, OW, N, dtype=dtype, device=DEV)
     ssum, ssq = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
     o.stem_conv_fwd(x.to(DEV), wk, y, 2, 1, stats=(ssum, ssq))
+    from sy11 import _lib
+    tiled = dtype != torch.float32 and N in (32, 64)                          # csrc/tune.h: 1 gather, 3 / 4 tiled
+    assert _lib.get_option("stem_fwd_last") == ((3 if W % 4 == 0 else 4) if tiled else 1)
     # N = 32 / 64 in 16 bit runs on the MFMA, which rounds the image to the compute dtype exactly as autocast does in the
     # reference; the other widths take the f32 VALU kernel that multiplies the f32 image directly
     xq = q(x, dtype) if N in (32, 64) else x
@@ -469,6 +475,7 @@ def test_stem_conv(N, H, W, dtype):
     dy = rnd(B, N, OH, OW, seed=3)
     dw = torch.zeros(N, 3, 3, 3, dtype=torch.float32, device=DEV)
     o.stem_conv_wgrad(x.to(DEV), nhwc(dy, dtype), dw, 2, 1)
+    assert _lib.get_option("stem_wgrad_last") == ((3 if W % 4 == 0 else 4) if tiled else 1)
     close(dw.cpu().permute(0, 3, 1, 2), torch.nn.grad.conv2d_weight(xq, (N, 3, 3, 3), q(dy, dtype), 2, 1), torch.float32,
           "stem wgrad", mult=8)
 
