@@ -58,6 +58,7 @@ const char* sy11_last_error(void);
  *   "igemm_deep" 0|1|2 (deeper LDS rings), "igemm_bpol" 0|1|2 (cache policy of the filter-row copies),
  *   "dgrad_s2_halo" 0|1 (3x3 stride-2 input gradient: four igemm launches, one per output parity / ONE fused-parity pass),
  *   "row_map" 0|1 (row walk of the BatchNorm and copy kernels: strided grid of r01 / contiguous chunk per workgroup),
+ *   "maxpool_sep" 0|1 (5x5 max-pool of 16-bit tensors with 16-byte channel vectors: 25-way kernels / separable forward and column-walk backward),
  *   "deterministic" 0|1   ordered reductions (cfg/default.yaml:29 `deterministic: True`, utils/torch_utils.py:474-492): every sum
  *                         across workgroups — BatchNorm statistics and backward sums, filter / bias gradients, loss partials —
  *                         goes through one partial row per workgroup and a fixed-shape fold instead of f32 atomics; bit-identical
@@ -65,7 +66,7 @@ const char* sy11_last_error(void);
  *                         rows live in a per-stream workspace the LIBRARY allocates (grown during eager warm-up, never under capture).
  *                         Cost on the headline workload: +3.8 ... +4.9 % per training step (r04).
  * Defaults come from the environment (SY11_TUNE, SY11_TUNE_LOG, SY11_IGEMM_CFG, SY11_WGRAD_CFG, SY11_IGEMM_KORDER,
- * SY11_IGEMM_DEEP, SY11_IGEMM_BPOL, SY11_DGRAD_S2_HALO, SY11_ROW_MAP, SY11_DETERMINISTIC).  Process-wide; set them between
+ * SY11_IGEMM_DEEP, SY11_IGEMM_BPOL, SY11_DGRAD_S2_HALO, SY11_ROW_MAP, SY11_DETERMINISTIC, SY11_MAXPOOL_SEP).  Process-wide; set them between
  * launches, not concurrently with them.                                                                                */
 int sy11_set_option(const char* name, int32_t value);
 int sy11_get_option(const char* name, int32_t* value);
@@ -75,7 +76,11 @@ int sy11_get_option(const char* name, int32_t* value);
  * table; -1 before the first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.
  * Likewise stem_fwd_last and stem_wgrad_last: which first-layer kernel (csrc/direct.hip) the most recent sy11_stem_conv_fwd[_bn] /
  * sy11_stem_conv_wgrad launched — 1 gather, 2 MFMA gather, 3 LDS-tiled with 16-byte image loads, 4 LDS-tiled with element-wise
- * fill; -1 before the first launch.                                                                                          */
+ * fill; -1 before the first launch.
+ * pool_fwd_last and pool_bwd_last: which 5x5 max-pool kernel the most recent sy11_maxpool5_fwd / sy11_maxpool5_bwd launched —
+ * 1 25-way with one element per thread, 2 25-way with 16-byte channel vectors, 3 the separable forward / column-walk backward.
+ * ew_vec_last: the channel-vector width in elements (1, 4 or 8) of the most recent sy11_copy2d / sy11_upsample2x_fwd /
+ * sy11_upsample2x_bwd launch.  Both -1 before the first launch.                                                              */
 /* The autotuner's pick tables as a flat array of 16-byte records {u64 problem hash, i32 kind, i32 pick}: export on one
  * rank, broadcast, import on the others, so every rank of a data-parallel job (engine/trainer.py:217-228) runs the same
  * kernels.  sy11_tune_export returns the number of bytes needed (pass buf = NULL to size the buffer).                 */

@@ -19,7 +19,7 @@ extern "C" const char* sy11_last_error(void) { return g_err; }
 // ------------------------------------------------------------------------------------------------ run-time options
 static int g_opt[OPT_COUNT];
 static std::once_flag g_opt_once;
-static const char* const kOptName[OPT_COUNT] = {"tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo", "row_map", "deterministic"};
+static const char* const kOptName[OPT_COUNT] = {"tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo", "row_map", "deterministic", "maxpool_sep"};
 static void opt_init() {
   auto env = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
   g_opt[OPT_TUNE] = env("SY11_TUNE", 1) != 0;
@@ -32,18 +32,19 @@ static void opt_init() {
   g_opt[OPT_DGRAD_S2_HALO] = env("SY11_DGRAD_S2_HALO", 1);
   g_opt[OPT_ROW_MAP] = env("SY11_ROW_MAP", 1);
   g_opt[OPT_DETERMINISTIC] = env("SY11_DETERMINISTIC", 0) != 0;
+  g_opt[OPT_MAXPOOL_SEP] = env("SY11_MAXPOOL_SEP", 1);
 }
 int sy11_opt(int which) {
   std::call_once(g_opt_once, opt_init);
   return g_opt[which];
 }
 // last launched configuration per table (tune.h): plain ints, written by the launching thread
-static int g_last_cfg[4] = {-1, -1, -1, -1};
-static const char* const kLastCfgName[4] = {"igemm_last_cfg", "wgrad_last_cfg", "stem_fwd_last", "stem_wgrad_last"};
+static int g_last_cfg[SY11_NOTE_KINDS] = {-1, -1, -1, -1, -1, -1, -1};
+static const char* const kLastCfgName[SY11_NOTE_KINDS] = {"igemm_last_cfg", "wgrad_last_cfg", "stem_fwd_last", "stem_wgrad_last", "pool_fwd_last", "pool_bwd_last", "ew_vec_last"};
 void sy11_note_cfg(int kind, int cfg) { g_last_cfg[kind] = cfg; }
 static int last_cfg_index(const char* name) {
   if (name)
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < SY11_NOTE_KINDS; ++i)
       if (!strcmp(name, kLastCfgName[i])) return i;
   return -1;
 }
@@ -56,7 +57,7 @@ static int opt_index(const char* name) {
 extern "C" int sy11_set_option(const char* name, int32_t value) {
   const int i = opt_index(name);
   SY11_REQUIRE(last_cfg_index(name) < 0, "set_option: '%s' is read-only (the configuration of the last launch)", name);
-  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic; read-only: igemm_last_cfg, wgrad_last_cfg, stem_fwd_last, stem_wgrad_last)", name ? name : "(null)");
+  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic, maxpool_sep; read-only: igemm_last_cfg, wgrad_last_cfg, stem_fwd_last, stem_wgrad_last, pool_fwd_last, pool_bwd_last, ew_vec_last)", name ? name : "(null)");
   std::call_once(g_opt_once, opt_init);
   g_opt[i] = value;
   return SY11_OK;

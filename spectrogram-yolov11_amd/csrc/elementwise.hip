@@ -570,6 +570,7 @@ extern "C" int sy11_copy2d(int32_t dtype, int64_t M, int32_t C, const void* src,
   const RowWalk w = row_walk(M, g.rows_pb, 4, 1, 1L << 20);
   dim3 grid(w.grid, g.cblocks), block(256);
   hipStream_t st = (hipStream_t)stream;
+  sy11_note_cfg(SY11_NOTE_EW_VEC, v ? 16 / esz : 1);
   SY11_DISPATCH_DTYPE(dtype, T, {
     constexpr int VE = 16 / (int)sizeof(T);
     if (v) hipLaunchKernelGGL((copy2d_kernel<T, VE>), grid, block, 0, st, (long)M, C, (const T*)src, src_ld, (T*)dst, dst_ld, accumulate, g.cpv, g.rows_pb, w);
@@ -649,6 +650,7 @@ extern "C" int sy11_upsample2x_fwd(int32_t dtype, int32_t B, int32_t H, int32_t 
   const RowGeom g = row_geom(C, v ? 16 / esz : 1);
   dim3 grid(row_grid((long)B * H * W, g.rows_pb), g.cblocks), block(256);
   hipStream_t st = (hipStream_t)stream;
+  sy11_note_cfg(SY11_NOTE_EW_VEC, v ? 16 / esz : 1);
   SY11_DISPATCH_DTYPE(dtype, T, {
     constexpr int VE = 16 / (int)sizeof(T);
     if (v) hipLaunchKernelGGL((upsample2x_fwd_kernel<T, VE>), grid, block, 0, st, B, H, W, C, (const T*)x, x_ld, (T*)y, y_ld, g.cpv, g.rows_pb);
@@ -666,6 +668,7 @@ extern "C" int sy11_upsample2x_bwd(int32_t dtype, int32_t B, int32_t H, int32_t 
   const RowGeom g = row_geom(C, v ? 16 / esz : 1);
   dim3 grid(row_grid((long)B * H * W, g.rows_pb), g.cblocks), block(256);
   hipStream_t st = (hipStream_t)stream;
+  sy11_note_cfg(SY11_NOTE_EW_VEC, v ? 16 / esz : 1);
   SY11_DISPATCH_DTYPE(dtype, T, {
     constexpr int VE = 16 / (int)sizeof(T);
     if (v) hipLaunchKernelGGL((upsample2x_bwd_kernel<T, VE>), grid, block, 0, st, B, H, W, C, (const T*)dy, dy_ld, (T*)dx, dx_ld, accumulate, g.cpv, g.rows_pb);
@@ -678,7 +681,12 @@ extern "C" int sy11_upsample2x_bwd(int32_t dtype, int32_t B, int32_t H, int32_t 
 // ------------------------------------------------------------------------------------------------ 5x5 stride-1 max pool
 // Both kernels are branch-free over the 25 window positions: a position outside the map loads a clamped (always legal) pixel and is
 // neutralised arithmetically, so the 5 loads of a window row go out back to back instead of one branch-and-wait per position.
-// ATen's rule: the first maximum in row-major window order wins, NaN propagates.
+// ATen's rule: the first maximum in row-major window order wins, and a NaN of either sign propagates, the last one in the window
+// naming the position.  The f32 branch keeps exactly that.  The three 16-bit key forms (here, the separable forward, and through the
+// recorded positions the two backwards) keep the first-maximum rule on everything that is not a NaN, and order NaNs by their bits:
+// a NaN with a clear sign bit outranks +inf and propagates, among such NaNs the larger payload wins and then the earlier position;
+// a NaN with the sign bit set is ordered below -inf and does not propagate (a window of nothing else returns it).  That is accepted
+// because SPPF concatenates the unpooled input beside the three pooled maps, so a NaN of either sign still reaches cv2.
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void maxpool5_fwd_kernel(int B, int H, int W, int C, const T* __restrict__ x, int x_ld, T* __restrict__ y, int y_ld,
                                                            uint8_t* __restrict__ idx, int cpv, int rows_pb) {
@@ -757,7 +765,7 @@ __global__ __launch_bounds__(256) void maxpool5_fwd_kernel(int B, int H, int W, 
           const bool ok = ((rmask >> wy) & (cmask >> wx) & 1u) != 0;
 #pragma unroll
           for (int i = 0; i < VEC; ++i)
-            if (ok && v[wx][i] > best[i]) { best[i] = v[wx][i]; bi[i] = wy * 5 + wx; }   // strict >: first maximum wins
+            if (ok && (v[wx][i] > best[i] || v[wx][i] != v[wx][i])) { best[i] = v[wx][i]; bi[i] = wy * 5 + wx; }   // strict >: first maximum wins; a NaN always does
         }
       }
     }
@@ -991,9 +999,8 @@ extern "C" int sy11_maxpool5_fwd(int32_t dtype, int32_t B, int32_t H, int32_t W,
   const RowGeom g = row_geom(C, v ? 16 / esz : 1);
   dim3 grid(row_grid((long)B * H * W, g.rows_pb), g.cblocks), block(256);
   hipStream_t st = (hipStream_t)stream;
-  static int sep_env = -1;
-  if (sep_env < 0) { const char* e = getenv("SY11_MAXPOOL_SEP"); sep_env = e ? atoi(e) : 1; }
-  if (sep_env && v && esz == 2) {                      // separable row / column maxima, 5 rows of one column per thread
+  sy11_note_cfg(SY11_NOTE_POOL_FWD, sy11_opt(OPT_MAXPOOL_SEP) && v && esz == 2 ? SY11_POOL_WALK : (v ? SY11_POOL_VEC : SY11_POOL_SCALAR));
+  if (sy11_opt(OPT_MAXPOOL_SEP) && v && esz == 2) {                      // separable row / column maxima, 5 rows of one column per thread
     constexpr int RR = 5;
     const int bands = (H + RR - 1) / RR, cpv8 = C / 8;
     const long total = (long)B * bands * W * cpv8;
@@ -1020,9 +1027,8 @@ extern "C" int sy11_maxpool5_bwd(int32_t dtype, int32_t B, int32_t H, int32_t W,
   const RowGeom g = row_geom(C, v ? 16 / esz : 1);
   dim3 grid(row_grid((long)B * H * W, g.rows_pb), g.cblocks), block(256);
   hipStream_t st = (hipStream_t)stream;
-  static int walk_env = -1;
-  if (walk_env < 0) { const char* e = getenv("SY11_MAXPOOL_SEP"); walk_env = e ? atoi(e) : 1; }
-  if (walk_env && v && esz == 2) {                     // five rows of one column per thread, each row of (dy, argmax) pairs loaded once
+  sy11_note_cfg(SY11_NOTE_POOL_BWD, sy11_opt(OPT_MAXPOOL_SEP) && v && esz == 2 ? SY11_POOL_WALK : (v ? SY11_POOL_VEC : SY11_POOL_SCALAR));
+  if (sy11_opt(OPT_MAXPOOL_SEP) && v && esz == 2) {                     // five rows of one column per thread, each row of (dy, argmax) pairs loaded once
     constexpr int RR = 5;
     const int bands = (H + RR - 1) / RR, cpv8 = C / 8;
     const long total = (long)B * bands * W * cpv8;

@@ -20,20 +20,29 @@ constexpr int SY11_WGRAD_NCFG = 20;
 #include <unordered_map>
 
 // process-wide options (core.hip): defaults come from the environment (SY11_TUNE, SY11_TUNE_LOG, SY11_IGEMM_CFG,
-// SY11_WGRAD_CFG, SY11_IGEMM_KORDER, SY11_IGEMM_DEEP, SY11_IGEMM_BPOL), sy11_set_option() changes them at run time
-enum Sy11Opt { OPT_TUNE = 0, OPT_TUNE_LOG, OPT_IGEMM_CFG, OPT_WGRAD_CFG, OPT_IGEMM_KORDER, OPT_IGEMM_DEEP, OPT_IGEMM_BPOL, OPT_DGRAD_S2_HALO, OPT_ROW_MAP, OPT_DETERMINISTIC, OPT_COUNT };
+// SY11_WGRAD_CFG, SY11_IGEMM_KORDER, SY11_IGEMM_DEEP, SY11_IGEMM_BPOL, SY11_MAXPOOL_SEP), sy11_set_option() changes them at run time
+enum Sy11Opt { OPT_TUNE = 0, OPT_TUNE_LOG, OPT_IGEMM_CFG, OPT_WGRAD_CFG, OPT_IGEMM_KORDER, OPT_IGEMM_DEEP, OPT_IGEMM_BPOL, OPT_DGRAD_S2_HALO, OPT_ROW_MAP, OPT_DETERMINISTIC, OPT_MAXPOOL_SEP, OPT_COUNT };
 int sy11_opt(int which);
 // the configuration of the most recent launch of each table (core.hip), read-only through sy11_get_option as "igemm_last_cfg" /
 // "wgrad_last_cfg"; -1 before the first launch.  One host-side int store per launch: tests read back which kernel they checked.
 // The fused-parity stride-2 input gradient (conv3x3.hip halo_dgrad_s2_kernel) is no entry of the igemm table: it records this value.
 constexpr int SY11_CFG_HALO_DGRAD_S2 = 100;
-void sy11_note_cfg(int kind, int cfg);      // kind 0 = igemm (fwd / dgrad), 1 = wgrad, 2 = stem forward, 3 = stem filter gradient
+void sy11_note_cfg(int kind, int cfg);      // kind 0 = igemm (fwd / dgrad), 1 = wgrad, 2 = stem forward, 3 = stem filter gradient,
+                                            // 4 = 5x5 pool forward, 5 = 5x5 pool backward, 6 = channel-vector width of a data-movement launch
+constexpr int SY11_NOTE_KINDS = 7;
 // which of the first layer's kernels (direct.hip) the last sy11_stem_conv_fwd[_bn] / sy11_stem_conv_wgrad launched, read-only as
 // "stem_fwd_last" / "stem_wgrad_last" (kinds 2 / 3 of sy11_note_cfg); -1 before the first launch
 constexpr int SY11_STEM_GATHER = 1;         // stem_fwd_kernel / stem_wgrad_kernel: any dtype, N, leading dimension, geometry
 constexpr int SY11_STEM_MMA = 2;            // stem_fwd_mma / stem_wgrad_mma: MFMA, operands gathered from the image
 constexpr int SY11_STEM_TILE_VEC = 3;       // stem_fwd_tile / stem_wgrad_tile, image rows by 16-byte loads
 constexpr int SY11_STEM_TILE_SCALAR = 4;    // stem_fwd_tile / stem_wgrad_tile, image rows element by element
+// which 5x5 max-pool kernel (elementwise.hip) the last sy11_maxpool5_fwd / sy11_maxpool5_bwd launched, read-only as "pool_fwd_last" /
+// "pool_bwd_last" (kinds 4 / 5); "maxpool_sep" 0 (SY11_MAXPOOL_SEP) keeps the 16-bit vector case on the 25-way kernels
+constexpr int SY11_POOL_SCALAR = 1;         // maxpool5_fwd_kernel / maxpool5_bwd_kernel<T, 1>: 25-way, one element per thread
+constexpr int SY11_POOL_VEC = 2;            // maxpool5_fwd_kernel / maxpool5_bwd_kernel<T, 16 / sizeof(T)>: 25-way, 16-byte channel vectors
+constexpr int SY11_POOL_WALK = 3;           // maxpool5_fwd_sep_kernel / maxpool5_bwd_walk_kernel: 16-bit, five rows of one column per thread
+// "ew_vec_last" (kind 6): the channel-vector width (1, 4 or 8 elements) of the last sy11_copy2d / sy11_upsample2x_fwd / sy11_upsample2x_bwd
+constexpr int SY11_NOTE_POOL_FWD = 4, SY11_NOTE_POOL_BWD = 5, SY11_NOTE_EW_VEC = 6;
 
 namespace sy11tune {
 

@@ -234,14 +234,16 @@ def call(name: str, *args):
 
 def set_option(name: str, value: int):
     """sy11_set_option: "tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo",
-    "row_map", "deterministic".  "igemm_last_cfg" / "wgrad_last_cfg" / "stem_fwd_last" / "stem_wgrad_last" are read-only
-    (get_option) and refused here."""
+    "row_map", "deterministic", "maxpool_sep".  "igemm_last_cfg" / "wgrad_last_cfg" / "stem_fwd_last" / "stem_wgrad_last" /
+    "pool_fwd_last" / "pool_bwd_last" / "ew_vec_last" are read-only (get_option) and refused here."""
     check(load().sy11_set_option(name.encode(), int(value)), "sy11_set_option")
 
 
 def get_option(name: str) -> int:
     """sy11_get_option: every option of set_option, plus "igemm_last_cfg" / "wgrad_last_cfg" (the configuration of the last launch)
-    and "stem_fwd_last" / "stem_wgrad_last" (which first-layer kernel the last launch was: 1 gather, 2 MFMA gather, 3 / 4 LDS-tiled)."""
+    and "stem_fwd_last" / "stem_wgrad_last" (which first-layer kernel the last launch was: 1 gather, 2 MFMA gather, 3 / 4 LDS-tiled),
+    "pool_fwd_last" / "pool_bwd_last" (which 5x5 max-pool kernel: 1 25-way per element, 2 25-way per 16-byte vector, 3 column walk)
+    and "ew_vec_last" (channel-vector width, 1 / 4 / 8, of the last copy2d / upsample2x launch).  All are -1 before the first launch."""
     v = C.c_int32(0)
     check(load().sy11_get_option(name.encode(), C.byref(v)), "sy11_get_option")
     return int(v.value)

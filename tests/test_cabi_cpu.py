@@ -62,7 +62,7 @@ def test_run_time_options_round_trip_and_reject_unknown_names():
     from sy11 import _lib
     lib = _lib.load()
     names = re.findall(r'"([a-z0-9_]+)"', HEADER[HEADER.index("run-time options"):HEADER.index("int sy11_set_option")])
-    assert {"tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo", "row_map", "deterministic"} <= set(names)
+    assert {"tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo", "row_map", "deterministic", "maxpool_sep"} <= set(names)
     for n in set(names):
         old = _lib.get_option(n)
         try:
@@ -74,9 +74,9 @@ def test_run_time_options_round_trip_and_reject_unknown_names():
     # the configuration of the last launch: readable, -1 in a library that has launched nothing (always so without a GPU; in one
     # process with the GPU tests an earlier conv may have left its configuration), refused on set
     import torch
-    for n in ("igemm_last_cfg", "wgrad_last_cfg", "stem_fwd_last", "stem_wgrad_last"):
+    for n in ("igemm_last_cfg", "wgrad_last_cfg", "stem_fwd_last", "stem_wgrad_last", "pool_fwd_last", "pool_bwd_last", "ew_vec_last"):
         before = _lib.get_option(n)
-        top = 4 if n.startswith("stem") else 100
+        top = 4 if n.startswith("stem") else 3 if n.startswith("pool") else 8 if n.startswith("ew") else 100
         assert n in HEADER and (-1 <= before <= top if torch.cuda.is_available() else before == -1)
         assert lib.sy11_set_option(n.encode(), 3) == -1 and b"read-only" in lib.sy11_last_error() and _lib.get_option(n) == before
 
