@@ -838,6 +838,45 @@ int sy11_fec_check(int32_t n_frame, const sy11_fec_frame* frame_host, const sy11
                    const uint8_t* whiten, const sy11_fec_crc* crc, int64_t n_rows, int64_t stride_soft, const int8_t* soft, int64_t stride_bits,
                    const uint8_t* bits, int64_t stride_data, uint8_t* data, int32_t* rows, void* stream);
 
+/* ---- frame correction: the Reed-Solomon outer code behind the frame decoder, with its byte interleaver (spec in DESIGN.md §4) ----
+ * Two launches over all frames (sy11/data/correct.py).  Exact integer arithmetic; no atomics; a frame's result does not depend on the others.
+ *
+ * Field: GF(2^8) modulo `poly`, 9 bits with bit 8 set, primitive (x has order 255); alpha = 0x02.  Code: n bytes of which k carry information,
+ * 1 <= k < n <= 255, nroots = n - k in [1, 64], t = nroots / 2 (rounded down), fcr in [0, 254], prim in [1, 254] with gcd(prim, 255) = 1.  A
+ * codeword is the bytes c[0 .. n), c[0] the coefficient of x^(n-1); the first k are the information (systematic), the last nroots the parity.
+ * c is a codeword iff S_j = sum_i c[i] alpha^(prim (fcr + j) (n - 1 - i)) = 0 for j in [0, nroots).  n < 255 is the shortened code: the missing
+ * leading bytes are zero and not transmitted.  interleave = I in [1, 8] codewords lie byte by byte in a frame: byte offset + m of a frame's data
+ * row, m in [0, I n), is byte m / I of codeword m % I (data as the frame decoder's launch 3 wrote it: the de-whitened bits packed MSB first).
+ *
+ * Both launches take the frames as a table of int32 rows: frame i reads row row[i] of data (n_rows, stride_data) uint8 and writes that row of
+ * info (n_rows, stride_info) uint8, cw (n_rows, I, 2) int32 and rows (n_rows, 6) int32.  row: DEVICE, row_host: its HOST copy.  Checked before
+ * anything is launched: the code's fields and the field polynomial as above, every row inside the tables and named once, offset >= 0,
+ * offset + I n <= stride_data, I k <= stride_info, the alignment of the int32 tables.  Nothing is launched and nothing written on an error.
+ *
+ * Launch 1, sy11_rs_decode.  One work item per (frame, codeword w), received word r.  If a codeword c of the shortened code has Hamming
+ * distance d(c, r) <= t it is unique and is the result: errors = d(c, r), bit_errors = popcount(c ^ r).  Otherwise errors = -1, bit_errors = 0
+ * and the bytes pass through unchanged; so for a candidate of the full-length code that differs from r in an untransmitted byte, for a locator
+ * polynomial whose degree is not its number of roots among the 255 positions, and for a degree above t.  nroots = 1 is t = 0: detection only.
+ * info[row stride_info + w k + i] = c[i], i in [0, k): de-interleaved, codeword-major; the bytes of the row from I k on are not written.
+ * cw[(row I + w) 2 + 0 .. 1] = errors, bit_errors.  One wavefront per codeword, whole frames per workgroup.
+ *
+ * Launch 2, sy11_rs_check.  One work item per frame.  rows[6 row + 0 .. 5] = n_failed (codewords with errors -1), the sum of errors and the sum
+ * of bit_errors over the others, crc_calc, crc_recv (uint32 bit patterns), crc_ok (1 / 0, -1 without a crc).  crc: HOST, the Rocksoft model of
+ * sy11_fec_crc; width 0 = none, else 8, 16, 24 or 32 and below the 8 I k information bits.  crc_recv = the last width / 8 bytes of info's I k,
+ * MSB first; crc_calc runs over the bytes before them (with refin each byte LSB first).                                              */
+typedef struct sy11_rs_code {
+  int32_t n;                   /* bytes of a codeword, 2 .. 255                                                     */
+  int32_t k;                   /* of which information, 1 .. n - 1, n - k <= 64                                     */
+  int32_t fcr;                 /* the first of the consecutive roots, 0 .. 254                                      */
+  int32_t prim;                /* the roots are powers of alpha^prim, 1 .. 254, coprime to 255                      */
+  int32_t interleave;          /* codewords of a frame, 1 .. 8                                                      */
+  int32_t poly;                /* the field polynomial with its bit 8, primitive                                    */
+} sy11_rs_code;
+int sy11_rs_decode(int32_t n_frame, const int32_t* row_host, const int32_t* row, const sy11_rs_code* code, int32_t offset, int64_t n_rows,
+                   int64_t stride_data, const uint8_t* data, int64_t stride_info, uint8_t* info, int32_t* cw, void* stream);
+int sy11_rs_check(int32_t n_frame, const int32_t* row_host, const int32_t* row, const sy11_rs_code* code, const sy11_fec_crc* crc, int64_t n_rows,
+                  int64_t stride_info, const uint8_t* info, const int32_t* cw, int32_t* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,11 @@ class FecCrc(C.Structure):
     _fields_ = [("width", C.c_int32), ("poly", C.c_uint32), ("init", C.c_uint32), ("xorout", C.c_uint32), ("refin", C.c_int32), ("refout", C.c_int32)]
 
 
+class RsCode(C.Structure):
+    """sy11_rs_code: the Reed-Solomon code and interleaving depth of sy11_rs_decode / sy11_rs_check (include/sy11.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n", "k", "fcr", "prim", "interleave", "poly")]
+
+
 _vp, _i32, _i64, _f32, _f64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32, C.c_uint64
 _dp = C.POINTER(ConvDesc)
 _bp = C.POINTER(BnTail)
@@ -142,6 +147,8 @@ SIGNATURES = {
     "sy11_fec_soft": [_i32, _vp, _vp, _i32, _u64, _i64, _vp, _i64, _i64, _vp, _vp],
     "sy11_fec_viterbi": [_i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_fec_check": [_i32, _vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(FecCrc), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "sy11_rs_decode": [_i32, _vp, _vp, C.POINTER(RsCode), _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
+    "sy11_rs_check": [_i32, _vp, _vp, C.POINTER(RsCode), C.POINTER(FecCrc), _i64, _i64, _vp, _vp, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],

@@ -380,6 +380,13 @@ class YOLO:
         from ..data.decode import decode_frames
         return decode_frames(frames, demodulation, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
 
+    def correct(self, decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=None):
+        """Correct every frame of ``decoded`` with the Reed-Solomon outer code on the GPU -> ``sy11.data.correct.Corrected``: per frame the information bytes of
+        its ``interleave`` de-interleaved codewords, the byte errors corrected in each (-1: beyond the code) and whether the CRC over them holds
+        (``DetectionPredictor.correct``)."""
+        from ..data.correct import correct_decoded
+        return correct_decoded(decoded, code=code, interleave=interleave, offset=offset, crc=crc)
+
 
 def _device_list(device):
     """`device=0`, `"0,1"`, `[0, 1]`, `"cuda:1"` -> list of GPU indices (utils/torch_utils.py select_device's parsing)."""

@@ -335,6 +335,20 @@ class DetectionPredictor:
         from ..data.decode import decode_frames
         return decode_frames(frames, demodulation, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
 
+    def correct(self, decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=None):
+        """Remove the byte errors the Viterbi decoder left in every frame of ``decoded`` (what ``decode`` returned) with the Reed-Solomon outer code ->
+        ``sy11.data.correct.Corrected``, one row per frame in the frames' order (``csrc/rs.hip``).  ``code``: a name of ``sy11.data.correct.CODES``
+        ("dvb-204-188", "rs-255-239", "ccsds-255-223", "ccsds-255-239") or a dict n, k, poly, fcr, prim over GF(2^8); the CCSDS presets use the
+        conventional basis, the dual basis is out of scope.  A frame holds ``interleave`` codewords (1 .. 8), interleaved byte by byte from byte
+        ``offset`` of its de-whitened bytes.  All frames and codewords go through TWO launches: every codeword, one wavefront each, is de-interleaved
+        and corrected by up to ``(n - k) // 2`` byte errors in exact integer arithmetic (syndromes, Berlekamp-Massey, a Chien search, Forney's
+        formula) - a codeword beyond that is reported in ``errors`` as -1 and passes through; then per frame the failed codewords, the corrected
+        byte and bit errors and, with ``crc`` (a name of ``sy11.data.decode.CRCS`` or a Rocksoft dict of whole bytes), the check over the information
+        bytes (``crc_ok``; ``message(k)`` is what precedes the check field).  A frame the decoder left out is a row with ``valid`` False and the reason
+        "undecoded".  Argument errors are ``ValueError``s raised before anything touches the device; without a valid frame nothing is launched."""
+        from ..data.correct import correct_decoded
+        return correct_decoded(decoded, code=code, interleave=interleave, offset=offset, crc=crc)
+
     def _scan_channels(self, iq, sample_rate, center_freq, overlap, batch, merge, merge_thres, stride_frames, start, resample_to,
                        tune_to, channels, oversample, select):
         """``scan`` through the filter bank.  Chunks are outermost: the selected bands' strip generators advance in lock-step over

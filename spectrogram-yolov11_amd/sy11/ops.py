@@ -1353,6 +1353,94 @@ def fec_check(soft, bits, frames, polys, n_info, data, rows, whiten=None, crc=No
     return data, rows
 
 
+def _rs_table(what, name, t, dtype, dev, n_rows=None, shape=None, least=1):
+    """A contiguous device table of ``dtype``: 2-D (rows, stride >= least), or of the trailing ``shape``."""
+    bad = not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() < 2 or t.shape[0] == 0 or t.shape[0] >= 2 ** 31 or not t.is_contiguous() \
+        or (dev is not None and t.device != dev) or (n_rows is not None and t.shape[0] != n_rows)
+    if not bad:
+        bad = tuple(t.shape[1:]) != tuple(shape) if shape is not None else (t.dim() != 2 or t.shape[1] < least or t.shape[1] >= 2 ** 31)
+    if bad or t.data_ptr() % t.element_size():
+        raise ValueError(f"{what}: `{name}` must be a non-empty contiguous {dtype} tensor on the device" +
+                         (f" of shape (rows,) + {tuple(shape)}" if shape is not None else f", (rows, stride) with a stride of at least {least}") +
+                         ("" if n_rows is None else f", of {n_rows} rows"))
+
+
+def _rs_args(what, code, interleave, frames, n_rows):
+    """The checks the two launches of the frame corrector share (the library repeats them) -> (the ``RsCode``, the int32 table of the frames' rows)."""
+    from .data.correct import gf_tables
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))     # noqa: E731
+    if not isinstance(code, dict) or set(code) - {"name"} != {"n", "k", "poly", "fcr", "prim"} or not all(is_int(code[key]) for key in ("n", "k", "poly", "fcr", "prim")):
+        raise ValueError(f"{what}: `code` must be a dict of the integers n, k, poly, fcr and prim, got {code!r}")
+    n, k, poly, fcr, prim = (int(code[key]) for key in ("n", "k", "poly", "fcr", "prim"))
+    if not 1 <= k < n <= 255 or n - k > 64:
+        raise ValueError(f"{what}: the code (n={n}, k={k}) is not 1 <= k < n <= 255 with n - k <= 64")
+    if not 0 <= fcr <= 254:
+        raise ValueError(f"{what}: fcr {fcr} is not in [0, 254]")
+    if not 1 <= prim <= 254 or math.gcd(prim, 255) != 1:
+        raise ValueError(f"{what}: prim {prim} is not in [1, 254] and coprime to 255")
+    if not is_int(interleave) or not 1 <= interleave <= 8:
+        raise ValueError(f"{what}: interleave {interleave!r} is not in [1, 8]")
+    gf_tables(poly, what)                                                       # 9 bits, primitive
+    fr = np.asarray(frames)
+    if fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31 or not np.issubdtype(fr.dtype, np.integer):
+        raise ValueError(f"{what}: `frames` must be a non-empty 1-D integer array of the rows the frames read")
+    row = fr.astype(np.int64)
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        i = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise ValueError(f"{what}: frame {i} reads row {int(row[i])} of a table of {n_rows} rows (a row takes one frame)")
+    return _lib.RsCode(n, k, fcr, prim, int(interleave), poly), np.ascontiguousarray(row.astype(np.int32))
+
+
+def rs_decode(data, frames, code, info, cw, interleave=1, offset=0):
+    """Launch 1 of the frame corrector (sy11_rs_decode): for every frame of ``frames`` (the rows they read, a 1-D integer array) the ``interleave`` Reed-Solomon
+    codewords of ``code`` (a dict n, k, poly, fcr, prim: ``sy11.data.correct.CODES``) that lie byte by byte from byte ``offset`` of ``data[row]`` (rows, stride)
+    uint8 are corrected by up to ``(n - k) // 2`` byte errors each.  ``info[row]`` (rows, stride >= interleave k) uint8 takes the information bytes, codeword after
+    codeword, and ``cw[row]`` (rows, interleave, 2) int32 the byte errors (-1: not correctable, the bytes pass through) and bit errors of each.  One wavefront
+    per codeword.  A refused call raises ``ValueError`` and writes nothing.  -> ``(info, cw)``."""
+    what = "rs_decode"
+    _rs_table(what, "data", data, torch.uint8, None)
+    dev, n_rows = data.device, data.shape[0]
+    spec, row = _rs_args(what, code, interleave, frames, n_rows)
+    _rs_table(what, "info", info, torch.uint8, dev, n_rows=n_rows, least=spec.interleave * spec.k)
+    _rs_table(what, "cw", cw, torch.int32, dev, n_rows=n_rows, shape=(spec.interleave, 2))
+    if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset < 0 or offset + spec.interleave * spec.n > data.shape[1]:
+        raise ValueError(f"{what}: the {spec.interleave} x {spec.n} bytes at offset {offset!r} leave the {data.shape[1]} bytes of a data row")
+    t = torch.from_numpy(row).to(dev)
+    call("sy11_rs_decode", row.shape[0], C.c_void_p(row.ctypes.data), _p(t), C.byref(spec), int(offset), n_rows, data.shape[1], _p(data), info.shape[1], _p(info), _p(cw),
+         _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return info, cw
+
+
+def rs_check(info, cw, frames, code, rows, interleave=1, crc=None):
+    """Launch 2 of the frame corrector (sy11_rs_check): for every frame of ``frames`` ``rows[row]`` (rows, 6) int32 takes n_failed (the codewords of ``cw[row]`` with -1),
+    the sums of byte and bit errors over the others, and crc_calc, crc_recv, crc_ok over the ``interleave k`` bytes of ``info[row]``: ``crc`` None (crc_ok = -1) or a
+    dict width / poly / init / refin / refout / xorout of whole bytes (``sy11.data.decode.CRCS``), the check field the last bytes, MSB first.  A refused call raises
+    ``ValueError`` and writes nothing.  -> ``rows``."""
+    what = "rs_check"
+    _rs_table(what, "info", info, torch.uint8, None)
+    dev, n_rows = info.device, info.shape[0]
+    spec, row = _rs_args(what, code, interleave, frames, n_rows)
+    n_bytes = spec.interleave * spec.k
+    _rs_table(what, "info", info, torch.uint8, dev, least=n_bytes)
+    _rs_table(what, "cw", cw, torch.int32, dev, n_rows=n_rows, shape=(spec.interleave, 2))
+    _rs_table(what, "rows", rows, torch.int32, dev, n_rows=n_rows, shape=(6,))
+    check = _lib.FecCrc()
+    if crc is not None:
+        try:
+            W, poly, init, xorout, refin, refout = (int(crc[key]) for key in ("width", "poly", "init", "xorout", "refin", "refout"))
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
+        if W not in (8, 16, 24, 32) or 8 * n_bytes <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) or refout not in (0, 1):
+            raise ValueError(f"{what}: the crc {crc!r} is not of 8, 16, 24 or 32 bits below the {8 * n_bytes} information bits, with fields of that width")
+        check = _lib.FecCrc(W, poly, init, xorout, refin, refout)
+    t = torch.from_numpy(row).to(dev)
+    call("sy11_rs_check", row.shape[0], C.c_void_p(row.ctypes.data), _p(t), C.byref(spec), C.byref(check), n_rows, info.shape[1], _p(info), _p(cw), _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return rows
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
