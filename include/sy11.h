@@ -779,6 +779,63 @@ int sy11_sync_peaks(int32_t n_item, const sy11_sync_item* item_host, const sy11_
 int sy11_sync_frames(int32_t n_frame, const sy11_sync_frame* frame_host, const sy11_sync_frame* frame, int64_t n_word, const uint8_t* words,
                      int64_t n_sym, const float* sym, int64_t n_rows, int32_t* rows, int64_t stride, uint8_t* bits, void* stream);
 
+/* ---- equalisation: the sync-word least-squares equaliser of every found frame (spec in DESIGN.md §4) ----
+ * Two launches (sy11/data/equalize.py), four when the taps are refined on the decisions of a first pass.  sym: the packed corrected symbols
+ * (complex64, what sy11_demod_decide wrote to r), never written; words: packed decisions of the words as the frame search takes them.
+ * taps = N, odd, 3 .. 15; D = (N - 1) / 2; a symbol outside its clip reads as 0.  A decision names a unit-modulus point: 1 - 2 d (order 2),
+ * ((1 - 2 (d >> 1)) + i (1 - 2 (d & 1))) s with s = the float64 nearest 1 / sqrt(2) (order 4).
+ *
+ * Launch 1, sy11_eq_solve.  One wavefront per frame: the word words[word_off  word_off + L) at position p of the clip sym[sym_off  sym_off + n_sym),
+ * found at rotation q, gain A.  Target t[k] = A point(word[k]) turned FORWARD by q steps of 2 pi / order (swaps and negations: exact) for k < L, and
+ * A point(decisions[sym_off + p + k]) for L <= k < Lt (decisions: what launch 2 wrote in a first pass; may be null when Lt == L everywhere).  In
+ * float64 from the stored float32 symbols, k ascending, with u_k[j] = r[p + k + D - j]:  R = sum_k conj(u_k) u_k^T,  z = sum_k conj(u_k) t[k];
+ * R += reg (tr R / N) I;  R = G G^H (Cholesky);  w = R^-1 z by the two triangular solves.  w[row 30 + 2 j + 0 .. 1] = Re, Im of tap j, zeros from j = N
+ * on.  rows[4 row + 0 .. 3] = mse_before = sum_(k<L) |r[p + k] - t[k]|^2 / (L A^2), mse_after = the same with w^T u_k for r[p + k], pivot_min = the
+ * smallest G[a][a]^2 / (tr R / N) (tr R before reg is added), ok = 1.  A pivot that is not finite and positive, or a tap that is not finite: ok = 0,
+ * w = the unit impulse at j = D, pivot_min = the failed pivot over tr R / N.  frame: DEVICE table, frame_host: its HOST copy, checked entry by entry
+ * before anything is launched: order 2 or 4, q < order, the clip inside sym[0  n_sym), 1 <= L <= 256, L <= Lt <= 4096, the word inside
+ * words[0  n_word), p >= 0 and p + Lt <= n_sym, the gain finite and positive, 0 <= reg <= 1, the row inside [0  n_rows) and written by one frame.
+ * A sum depends neither on the launch's grouping nor on the frame's place in it; no atomics.  Nothing is launched and nothing written on an error.
+ *
+ * Launch 2, sy11_eq_apply.  A segment is the symbols [start  end) of a clip with one owner: row `frame` of w, or -1.  An item is tile `tile` of
+ * TILE = the value of sy11_eq_tile symbols of segment `seg`.  With an owner  out[m] = f32(sum_j w[j] r[m + D - j]), in float64, j ascending,
+ * re += (wr a) - (wi b), im += (wr b) + (wi a), every product and sum rounded on its own and the result rounded once to float32; without one
+ * out[m] = sym[m] bit for bit.  decisions[m] = Re < 0 (order 2), 2 (Re < 0) + (Im < 0) (order 4) of out[m].  Checked: order 2 or 4, the clip inside
+ * sym[0  n_sym), 0 <= start < end <= n_sym, the owner -1 or a row of w, no symbol inside two segments; every item a tile of a segment, none twice;
+ * out is not sym.  No two items write the same symbol; no atomics.                                                                     */
+typedef struct sy11_eq_frame {
+  int64_t sym_off;             /* the clip's first symbol in the packed symbol buffer                              */
+  int64_t n_sym;               /* symbols of the clip                                                              */
+  int64_t word_off;            /* the word's first decision in the packed word buffer                              */
+  int64_t p;                   /* position of the word's first symbol in the clip                                  */
+  int32_t L;                   /* symbols of the word, 1 .. 256                                                    */
+  int32_t Lt;                  /* training symbols, L .. 4096; those from L on are read from `decisions`           */
+  int32_t order;               /* 2 or 4                                                                           */
+  int32_t q;                   /* rotation: the word's points are turned forward by q steps of 2 pi / order        */
+  int32_t row;                 /* row of w and rows the frame writes                                               */
+  int32_t reserved;            /* 0                                                                                */
+  double gain;                 /* A: the modulus of a clean symbol of the clip                                     */
+} sy11_eq_frame;
+typedef struct sy11_eq_segment {
+  int64_t sym_off;             /* the clip's first symbol in the packed symbol buffer                              */
+  int64_t n_sym;               /* symbols of the clip                                                              */
+  int64_t start;               /* first symbol of the segment in the clip                                          */
+  int64_t end;                 /* one past its last                                                                */
+  int32_t frame;               /* the row of w that owns the segment, or -1: copied                                */
+  int32_t order;               /* 2 or 4                                                                           */
+} sy11_eq_segment;
+typedef struct sy11_eq_item {
+  int32_t seg;                 /* the segment                                                                      */
+  int32_t tile;                /* symbols [start + tile TILE  min(start + (tile + 1) TILE, end)) of it              */
+} sy11_eq_item;
+int32_t sy11_eq_tile(void);                       /* TILE: symbols per item of launch 2, a constant of the build */
+int sy11_eq_solve(int32_t n_frame, const sy11_eq_frame* frame_host, const sy11_eq_frame* frame, int32_t taps, double reg, int64_t n_word,
+                  const uint8_t* words, int64_t n_sym, const float* sym, const uint8_t* decisions, int64_t n_rows, double* w, double* rows,
+                  void* stream);
+int sy11_eq_apply(int32_t n_item, const sy11_eq_item* item_host, const sy11_eq_item* item, int32_t n_seg, const sy11_eq_segment* seg_host,
+                  const sy11_eq_segment* seg, int32_t taps, int64_t n_rows, const double* w, int64_t n_sym, const float* sym, float* out,
+                  uint8_t* decisions, void* stream);
+
 /* ---- frame decoding: soft bits, the Viterbi decoder of the rate 1/2, K = 7 code, de-whitening and CRC of every frame (spec in DESIGN.md §4) ----
  * Three launches over all frames (sy11/data/decode.py).  A frame's received stream starts at symbol sym_off of the packed corrected symbols
  * sym (complex64, what sy11_demod_decide wrote to r): the first symbol after its sync word.  w = log2(order) bits per symbol.  A frame has T

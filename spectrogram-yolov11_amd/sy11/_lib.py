@@ -144,6 +144,8 @@ SIGNATURES = {
     "sy11_sync_correlate": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_sync_peaks": [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp],
     "sy11_sync_frames": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "sy11_eq_solve": [_i32, _vp, _vp, _i32, _f64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp],
+    "sy11_eq_apply": [_i32, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "sy11_fec_soft": [_i32, _vp, _vp, _i32, _u64, _i64, _vp, _i64, _i64, _vp, _vp],
     "sy11_fec_viterbi": [_i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_fec_check": [_i32, _vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(FecCrc), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
@@ -173,6 +175,7 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_iq_cyclo_group": ([], C.c_int32),
          "sy11_iq_demod_tile": ([], C.c_int32),
          "sy11_sync_tile": ([], C.c_int32),
+         "sy11_eq_tile": ([], C.c_int32),
          "sy11_fec_tmax": ([], C.c_int32),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}
 

@@ -374,6 +374,13 @@ class YOLO:
         from ..data.frames import find_frames
         return find_frames(demodulation, words, payload=payload, threshold=threshold, max_errors=max_errors, t0=t0)
 
+    def equalize(self, frames, demodulation, *, taps=7, reg=1e-3, refine=0):
+        """Equalise every frame of ``frames`` (found in ``demodulation``) on the GPU -> ``sy11.data.equalize.Equalized``: per frame the least-squares taps of a symbol-spaced
+        FIR trained on its sync word, applied to the symbols the frame owns; ``find_frames`` and ``decode`` take the result in place of the demodulation
+        (``DetectionPredictor.equalize``)."""
+        from ..data.equalize import equalize_frames
+        return equalize_frames(frames, demodulation, taps=taps, reg=reg, refine=refine)
+
     def decode(self, frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
         """Decode every frame of ``frames`` (found in ``demodulation``) on the GPU -> ``sy11.data.decode.Decoded``: per frame the Viterbi-decoded, de-whitened
         information bits, the channel bit errors against the re-encoded decision and whether the CRC holds (``DetectionPredictor.decode``)."""

@@ -320,6 +320,21 @@ class DetectionPredictor:
         from ..data.frames import find_frames
         return find_frames(demodulation, words, payload=payload, threshold=threshold, max_errors=max_errors, t0=t0)
 
+    def equalize(self, frames, demodulation, *, taps=7, reg=1e-3, refine=0):
+        """Undo the multipath of every frame of ``frames`` (what ``find_frames`` returned for ``demodulation``) -> ``sy11.data.equalize.Equalized``, which ``find_frames`` and
+        ``decode`` take in place of the demodulation (``csrc/equalize.hip``).  The frame search says where each known word sits and at which rotation, so the
+        equaliser is feed-forward, in TWO launches over all frames and clips: per frame, one wavefront solves the regularised least-squares problem
+        (``reg``, relative to the mean diagonal) for the ``taps`` (odd, 3 .. 15) taps of a symbol-spaced FIR that maps the received word onto the word as sent,
+        by a Cholesky factorisation in float64; then the taps of each frame filter the symbols it owns, from its word to the end of its payload, of
+        overlapping frames the later one, in float64 and one fixed order, and every other symbol is copied bit for bit.  With ``refine`` beyond the word's
+        length both launches run again, trained on ``refine`` symbols of which those after the word are the first pass's decisions.  The symbols keep
+        the clip's rotation and gain.  Per frame ``Equalized.frames`` lists ``mse_before`` / ``mse_after`` over the word and the smallest pivot; a frame whose word is
+        shorter than twice the taps ("word"), whose clip has no positive gain ("gain") or is not valid ("clip"), or whose system is singular ("singular")
+        is a row with ``valid`` False and its symbols pass through.  Argument errors are ``ValueError``s raised before anything touches the device; without a
+        valid frame nothing is launched."""
+        from ..data.equalize import equalize_frames
+        return equalize_frames(frames, demodulation, taps=taps, reg=reg, refine=refine)
+
     def decode(self, frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
         """Turn the channel bits of every frame of ``frames`` (what ``find_frames`` returned for ``demodulation``) into a checked message ->
         ``sy11.data.decode.Decoded``, one row per frame in the frames' order (``csrc/fec.hip``).  The frames are coded with the rate 1/2, K = 7

@@ -1189,6 +1189,174 @@ def sync_frames(sym, frames, words, rows, bits):
     return rows, bits
 
 
+class EqRefused(_lib.Sy11Error, ValueError):
+    """A refusal of ``eq_solve`` / ``eq_apply``, raised by the checks here or by the library's: a ``ValueError`` that is also the library's error."""
+
+
+def _eq_call(name, *args):
+    try:
+        call(name, *args)
+    except _lib.Sy11Error as e:
+        raise EqRefused(str(e)) from None
+
+
+def _eq_taps(what, taps):
+    from .data.equalize import TAPS_MAX, TAPS_MIN
+    if isinstance(taps, bool) or not isinstance(taps, (int, np.integer)) or not TAPS_MIN <= taps <= TAPS_MAX or taps % 2 == 0:
+        raise EqRefused(f"{what}: {taps!r} taps are not an odd number in [{TAPS_MIN}, {TAPS_MAX}]")
+    return int(taps)
+
+
+def _eq_w(what, w, dev):
+    from .data.equalize import TAPS_MAX
+    if w.dtype != torch.complex128 or w.dim() != 2 or w.shape[1] != TAPS_MAX or w.shape[0] == 0 or w.shape[0] >= 2 ** 31 or not w.is_contiguous() or w.device != dev \
+            or w.data_ptr() % 8:
+        raise EqRefused(f"{what}: `w` must be a non-empty contiguous (rows, {TAPS_MAX}) complex128 tensor on the symbols' device")
+
+
+def eq_solve(sym, frames, words, taps, reg, w, rows, decisions=None):
+    """Launch 1 of the equaliser (sy11_eq_solve): every frame of ``frames`` — ``sy11.data.equalize.EQFRAME`` records (sym_off, n_sym, word_off, p, L, Lt, order, q,
+    row, reserved, gain): the word ``words[word_off : word_off + L]`` at position ``p`` of the clip ``sym[sym_off : sym_off + n_sym]``, found at rotation ``q`` — writes the
+    ``taps`` least-squares taps to ``w[row]`` (rows, 15) complex128, zero-padded, and (mse_before, mse_after, pivot_min, ok) to ``rows[row]`` (rows, 4) float64.  The
+    training symbols from ``L`` to ``Lt`` take their targets from ``decisions`` (uint8, laid out as ``sym``: what ``eq_apply`` wrote).  A refused call raises a
+    ``ValueError`` and writes nothing.  -> ``(w, rows)``."""
+    from .data.equalize import EQFRAME, L_MAX, LT_MAX
+    what = "eq_solve"
+    _need_gpu(sym, words, w, rows)
+    if sym.dtype != torch.complex64 or sym.dim() != 1 or not sym.is_contiguous() or sym.shape[0] == 0 or sym.shape[0] >= 2 ** 31 or sym.data_ptr() % 8:
+        raise EqRefused(f"{what}: `sym` must be a non-empty 1-D contiguous 8-byte aligned complex64 device tensor below 2^31")
+    dev = sym.device
+    if words.dtype != torch.uint8 or words.dim() != 1 or words.shape[0] == 0 or words.shape[0] >= 2 ** 31 or not words.is_contiguous() or words.device != dev:
+        raise EqRefused(f"{what}: `words` must be a non-empty 1-D contiguous uint8 tensor on the symbols' device")
+    taps = _eq_taps(what, taps)
+    if isinstance(reg, bool) or not isinstance(reg, (int, float, np.integer, np.floating)) or not 0.0 <= float(reg) <= 1.0:
+        raise EqRefused(f"{what}: reg = {reg!r} is not in [0, 1]")
+    _eq_w(what, w, dev)
+    if rows.dtype != torch.float64 or rows.dim() != 2 or tuple(rows.shape) != (w.shape[0], 4) or not rows.is_contiguous() or rows.device != dev or rows.data_ptr() % 8:
+        raise EqRefused(f"{what}: `rows` must be a contiguous ({w.shape[0]}, 4) float64 tensor on the symbols' device")
+    if decisions is not None and (decisions.dtype != torch.uint8 or tuple(decisions.shape) != tuple(sym.shape) or not decisions.is_contiguous() or decisions.device != dev):
+        raise EqRefused(f"{what}: `decisions` must be a contiguous ({sym.shape[0]},) uint8 tensor on the symbols' device")
+    fr = np.ascontiguousarray(frames)
+    if fr.dtype != EQFRAME or fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31:
+        raise EqRefused(f"{what}: `frames` must be a non-empty 1-D array of sy11.data.equalize.EQFRAME records")
+    n_sym, n_word, n_rows = sym.shape[0], words.shape[0], w.shape[0]
+    sym_off, ns, word_off, p, gain = fr["sym_off"], fr["n_sym"], fr["word_off"], fr["p"], fr["gain"]
+    L, Lt, order, q, row = (fr[k].astype(np.int64) for k in ("L", "Lt", "order", "q", "row"))
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: order {int(order[k])} is not 2 or 4")
+    bad = (q < 0) | (q >= order)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: rotation {int(q[k])} is not below the order {int(order[k])}")
+    bad = (sym_off < 0) | (ns < 1) | (ns > n_sym) | (sym_off > n_sym - ns)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: the clip [{int(sym_off[k])}, {int(sym_off[k] + ns[k])}) leaves the {n_sym} packed symbols")
+    bad = (L < 1) | (L > L_MAX) | (Lt < L) | (Lt > LT_MAX)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: a word of {int(L[k])} and {int(Lt[k])} training symbols are not 1 .. {L_MAX} and word .. {LT_MAX}")
+    bad = (word_off < 0) | (word_off > n_word - L)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: the word [{int(word_off[k])}, {int(word_off[k] + L[k])}) leaves the {n_word} packed word symbols")
+    bad = (p < 0) | (p > ns - Lt)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: {int(Lt[k])} training symbols at position {int(p[k])} end after the clip's {int(ns[k])} symbols")
+    bad = (Lt != L) & (decisions is None)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k} trains on {int(Lt[k] - L[k])} symbols beyond its word, but the decisions are null")
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.isfinite(gain) & (gain > 0))
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: frame {k}: the gain {float(gain[k])} is not finite and positive")
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        k = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise EqRefused(f"{what}: frame {k} writes row {int(row[k])} of a table of {n_rows} rows (a row takes one frame)")
+    t = torch.from_numpy(fr.view(np.uint8)).to(dev)
+    _eq_call("sy11_eq_solve", fr.shape[0], C.c_void_p(fr.ctypes.data), C.c_void_p(t.data_ptr()), taps, float(reg), n_word, _p(words), n_sym,
+             C.c_void_p(torch.view_as_real(sym).data_ptr()), None if decisions is None else _p(decisions), n_rows, C.c_void_p(torch.view_as_real(w).data_ptr()), _p(rows),
+             _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return w, rows
+
+
+def eq_apply(sym, items, segments, taps, w, out, decisions):
+    """Launch 2 of the equaliser (sy11_eq_apply): every item of ``items`` — ``sy11.data.equalize.EQITEM`` records (seg, tile): tile ``tile`` of the symbols ``[start, end)`` of
+    the clip ``sym[sym_off : sym_off + n_sym]`` that ``segments[seg]`` (``EQSEGMENT`` records: sym_off, n_sym, start, end, frame, order) names — writes the symbols filtered by
+    the ``taps`` taps ``w[frame]``, or copied bit for bit where ``frame`` is -1, to ``out`` (laid out as ``sym``) and their decisions to ``decisions`` (uint8).  A refused call
+    raises a ``ValueError`` and writes nothing.  -> ``(out, decisions)``."""
+    from .data.equalize import EQITEM, EQSEGMENT
+    what = "eq_apply"
+    _need_gpu(sym, w, out, decisions)
+    if sym.dtype != torch.complex64 or sym.dim() != 1 or not sym.is_contiguous() or sym.shape[0] == 0 or sym.shape[0] >= 2 ** 31 or sym.data_ptr() % 8:
+        raise EqRefused(f"{what}: `sym` must be a non-empty 1-D contiguous 8-byte aligned complex64 device tensor below 2^31")
+    dev = sym.device
+    if out.dtype != torch.complex64 or tuple(out.shape) != tuple(sym.shape) or not out.is_contiguous() or out.device != dev or out.data_ptr() % 8 or out.data_ptr() == sym.data_ptr():
+        raise EqRefused(f"{what}: `out` must be a contiguous 8-byte aligned complex64 tensor of the symbols' length, on their device, and not the symbols themselves")
+    if decisions.dtype != torch.uint8 or tuple(decisions.shape) != tuple(sym.shape) or not decisions.is_contiguous() or decisions.device != dev:
+        raise EqRefused(f"{what}: `decisions` must be a contiguous ({sym.shape[0]},) uint8 tensor on the symbols' device")
+    taps = _eq_taps(what, taps)
+    _eq_w(what, w, dev)
+    sg, it = np.ascontiguousarray(segments), np.ascontiguousarray(items)
+    if sg.dtype != EQSEGMENT or sg.ndim != 1 or sg.shape[0] == 0 or sg.shape[0] >= 2 ** 31:
+        raise EqRefused(f"{what}: `segments` must be a non-empty 1-D array of sy11.data.equalize.EQSEGMENT records")
+    if it.dtype != EQITEM or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise EqRefused(f"{what}: `items` must be a non-empty 1-D array of sy11.data.equalize.EQITEM records")
+    T, n_sym, n_rows = _lib.load().sy11_eq_tile(), sym.shape[0], w.shape[0]
+    sym_off, ns, start, end = sg["sym_off"], sg["n_sym"], sg["start"], sg["end"]
+    frame, order = sg["frame"].astype(np.int64), sg["order"].astype(np.int64)
+    bad = (order != 2) & (order != 4)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: segment {k}: order {int(order[k])} is not 2 or 4")
+    bad = (sym_off < 0) | (ns < 1) | (ns > n_sym) | (sym_off > n_sym - ns)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: segment {k}: the clip [{int(sym_off[k])}, {int(sym_off[k] + ns[k])}) leaves the {n_sym} packed symbols")
+    bad = (start < 0) | (start >= end) | (end > ns)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: segment {k}: symbols [{int(start[k])}, {int(end[k])}) are not inside the clip's {int(ns[k])}")
+    bad = (frame < -1) | (frame >= n_rows)
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: segment {k}: owner {int(frame[k])} is not -1 or a row of the {n_rows} of w")
+    a = sym_off + start
+    o = np.argsort(a, kind="stable")
+    bad = (sym_off + end)[o][:-1] > a[o][1:]
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: segment {int(o[k + 1])} writes symbol {int(a[o][k + 1])}, which segment {int(o[k])} of this call writes")
+    seg, tile = it["seg"].astype(np.int64), it["tile"].astype(np.int64)
+    bad = (seg < 0) | (seg >= sg.shape[0])
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: item {k}: segment {int(seg[k])} is not one of the {sg.shape[0]}")
+    bad = (tile < 0) | (tile * T >= (end - start)[seg])
+    if bad.any():
+        k = _first(bad)
+        raise EqRefused(f"{what}: item {k}: tile {int(tile[k])} is not one of segment {int(seg[k])}'s {int((end - start)[seg[k]])} symbols")
+    a = a[seg] + tile * T
+    if np.unique(a).shape[0] != a.shape[0]:
+        o = np.argsort(a, kind="stable")
+        k = _first(a[o][1:] == a[o][:-1])
+        raise EqRefused(f"{what}: item {int(o[k + 1])} writes symbol {int(a[o][k + 1])}, which item {int(o[k])} of this call writes")
+    ts, ti = torch.from_numpy(sg.view(np.uint8)).to(dev), torch.from_numpy(it.view(np.uint8)).to(dev)
+    _eq_call("sy11_eq_apply", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(ti.data_ptr()), sg.shape[0], C.c_void_p(sg.ctypes.data), C.c_void_p(ts.data_ptr()), taps,
+             n_rows, C.c_void_p(torch.view_as_real(w).data_ptr()), n_sym, C.c_void_p(torch.view_as_real(sym).data_ptr()),
+             C.c_void_p(torch.view_as_real(out).data_ptr()), _p(decisions), _stream())
+    ts.record_stream(torch.cuda.current_stream(dev))
+    ti.record_stream(torch.cuda.current_stream(dev))
+    return out, decisions
+
+
 def _fec_table(what, name, t, dtype, dev, n_rows=None, width=None, lo=1, hi=None, even=False):
     """A contiguous (rows, stride) device table of ``dtype``; ``width``: the exact stride, else ``lo <= stride <= hi``."""
     bad = t.dtype != dtype or t.dim() != 2 or t.shape[0] == 0 or t.shape[0] >= 2 ** 31 or not t.is_contiguous() or t.device != dev \
