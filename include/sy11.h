@@ -73,7 +73,8 @@ int sy11_get_option(const char* name, int32_t* value);
 /* Two more names are READ-ONLY (sy11_get_option answers, sy11_set_option fails with a message): igemm_last_cfg and wgrad_last_cfg,
  * the tile configuration of the most recent forward / input-gradient launch and of the most recent filter-gradient launch
  * (csrc/igemm.hip 0..25, csrc/wgrad.hip 0..19; 100 = the fused-parity stride-2 input gradient, which is no entry of the igemm
- * table; -1 before the first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.
+ * table, and in wgrad_last_cfg the grouped launch of sy11_conv2d_wgrad_group, which is no entry of the wgrad table; -1 before the
+ * first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.
  * Likewise stem_fwd_last and stem_wgrad_last: which first-layer kernel (csrc/direct.hip) the most recent sy11_stem_conv_fwd[_bn] /
  * sy11_stem_conv_wgrad launched — 1 gather, 2 MFMA gather, 3 LDS-tiled with 16-byte image loads, 4 LDS-tiled with element-wise
  * fill; -1 before the first launch.
@@ -140,6 +141,33 @@ int sy11_conv2d_dgrad(const sy11_conv_desc* d, const void* dy, int32_t dy_ld, co
 /* dw[n,r,s,c] += sum_{b,oy,ox} dy[b,oy,ox,n] * x[b, oy*SH-PH+r*DH, ox*SW-PW+s*DW, c]   (dw is ALWAYS f32 and is
  * accumulated into: zero it for a fresh gradient).                                                         */
 int sy11_conv2d_wgrad(const sy11_conv_desc* d, const void* x, const void* dy, int32_t dy_ld, float* dw, void* stream);
+
+/* Several dense 16-bit filter gradients in ONE launch (the small-map layers of a backward pass: each alone has too few dW tiles
+ * to fill the chip without many pixel splits).  Per problem exactly the sum above, dw += x (*) dy, with the arguments and the
+ * checks of sy11_conv2d_wgrad; in addition: dtype F16 or BF16 (the same for every problem), groups == 1, 1 <= count <=
+ * SY11_WGRAD_GROUP_MAX.  All checks run before anything is launched.  The problems travel by value in the kernel's argument block:
+ * nothing is copied to the device or allocated, and `problems` may be freed as soon as the call returns.
+ * target_workgroups: how many workgroups the group is cut into (0 = one resident round of the chip); the split is the pure function
+ * below.  Partial sums meet in dw through f32 atomics: with the "deterministic" option on the call returns SY11_EUNSUPPORTED and
+ * launches nothing (the caller runs the problems through sy11_conv2d_wgrad, which has the ordered path).
+ * "wgrad_last_cfg" reads 100 after a grouped launch.                                                                          */
+#define SY11_WGRAD_GROUP_MAX 32
+typedef struct sy11_wgrad_problem {
+  sy11_conv_desc desc;
+  const void* x;
+  const void* dy;
+  float* dw;
+  int32_t dy_ld;
+  int32_t reserved;
+} sy11_wgrad_problem;
+int sy11_conv2d_wgrad_group(int32_t dtype, int32_t count, const sy11_wgrad_problem* problems, int32_t target_workgroups,
+                            void* stream);
+/* The work split of a grouped launch, host arithmetic only.  Problem i (M = B*OH*OW pixels, N filters, K = KH*KW*C columns) has
+ * tiles_i = ceil(N/128) * ceil(K/128) tiles and stages_i = ceil(M/64) stages.  chunk = max(8, ceil(sum tiles_i * stages_i /
+ * target_workgroups)); splits_i = ceil(stages_i / chunk); pix_per_split[i] = 64 * ceil(stages_i / splits_i); problem i owns the
+ * workgroups wg_start[i] .. wg_start[i+1] (count + 1 entries), tiles_i * ceil(M / pix_per_split[i]) of them, split-major.       */
+int sy11_wgrad_group_plan(int32_t count, const int32_t* M, const int32_t* N, const int32_t* K, int32_t target_workgroups,
+                          int32_t* pix_per_split, int32_t* wg_start);
 
 /* wt[c][t][n] = w[n][t][c]  (t = r*KW+s), same dtype; feeds sy11_conv2d_dgrad                               */
 int sy11_weight_transpose(int32_t dtype, int32_t N, int32_t T, int32_t C, const void* w, void* wt, void* stream);

@@ -27,7 +27,10 @@ int sy11_opt(int which);
 // "wgrad_last_cfg"; -1 before the first launch.  One host-side int store per launch: tests read back which kernel they checked.
 // The fused-parity stride-2 input gradient (conv3x3.hip halo_dgrad_s2_kernel) is no entry of the igemm table: it records this value.
 constexpr int SY11_CFG_HALO_DGRAD_S2 = 100;
-void sy11_note_cfg(int kind, int cfg);      // kind 0 = igemm (fwd / dgrad), 1 = wgrad, 2 = stem forward, 3 = stem filter gradient,
+// The grouped filter-gradient launch (wgrad.hip wgrad16g_kernel, sy11_conv2d_wgrad_group) is no entry of the wgrad table either (it
+// cannot be forced or imported): "wgrad_last_cfg" reads this value after it.
+constexpr int SY11_CFG_WGRAD_GROUP = 100;
+void sy11_note_cfg(int kind, int cfg);     // kind 0 = igemm (fwd / dgrad), 1 = wgrad, 2 = stem forward, 3 = stem filter gradient,
                                             // 4 = 5x5 pool forward, 5 = 5x5 pool backward, 6 = channel-vector width of a data-movement launch
 constexpr int SY11_NOTE_KINDS = 7;
 // which of the first layer's kernels (direct.hip) the last sy11_stem_conv_fwd[_bn] / sy11_stem_conv_wgrad launched, read-only as

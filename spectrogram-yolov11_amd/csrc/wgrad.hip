@@ -14,7 +14,7 @@
 #include "det.h"
 #include <stdlib.h>
 
-struct WgradArgs {
+struct WgradCore {
   const void* x;
   const void* dy;
   float* dw;
@@ -27,6 +27,8 @@ struct WgradArgs {
   int tiles, total;      // tiles per pixel split, tiles * splits
   int pix_per_split;     // multiple of BP
   long dw_split_stride;  // 0: every pixel split adds into the one dW (atomics); ordered mode: split s owns dw + s * stride (det.h)
+};
+struct WgradArgs : WgradCore {
   signed char tap_dy[64];
   signed char tap_dx[64];
 };
@@ -197,9 +199,13 @@ template <> struct Mma16<__bf16> {
 // for a quarter of the pixels of each stage (k-step = wave).  Per stage the block then reads each operand fragment from LDS
 // once instead of twice (16 KB instead of 32 KB for the same 16 MFMAs): the tile is LDS-read bound, not MFMA bound.  The
 // four partial tiles are folded through the (then free) staging buffers: wave w keeps fragment w and parks its other three.
-template <typename T, int TILE, bool PSPLIT = false>
-__global__ __launch_bounds__(256) void wgrad16_kernel(const WgradArgs a) {
+// The body of one workgroup, shared by the per-layer kernels (wgrad16_kernel) and the grouped one (wgrad16g_kernel): `vid` is the
+// workgroup's virtual id inside the problem `a` (< a.total), `tap(kt, dy, dx)` gives the input offset of tap kt (the per-layer
+// kernels read the table in their arguments, the grouped kernel derives it from the filter geometry).
+template <typename T, int TILE, bool PSPLIT, class TapFn>
+__device__ __forceinline__ void wgrad16_body(const WgradCore& args, const int vid, TapFn tap) {
   static_assert(!PSPLIT || TILE == 64, "PSPLIT is the 64-wide variant");
+  const WgradCore a = args;                       // a private copy: its fields live in scalar registers across the stores and atomics below
   constexpr int BP = 64;                          // pixels per stage (4 MFMA k-steps of 16)
   constexpr int ROWB = TILE * 2 + 64;             // LDS row stride in bytes
   constexpr int CPR = TILE / 8;                   // 16-byte chunks per tile row
@@ -210,11 +216,6 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgradArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * OPB];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware order: hardware deals linear workgroup ids round-robin to the 8 XCDs; give each XCD a contiguous run of
-  // (split, tile) pairs so all tiles of one pixel split — which re-read the same dy / x rows — share one L2.
-  const int per_xcd = gridDim.x >> 3;
-  const int vid = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  if (vid >= a.total) return;
   const int split = vid / a.tiles, tile = vid - split * a.tiles;
   const int tile_k = tile % a.tiles_k, tile_n = tile / a.tiles_k;
   const int n0 = tile_n * TILE, k0 = tile_k * TILE;
@@ -229,7 +230,8 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgradArgs a) {
   const int kk = k0 + chunk * 8;
   const bool k_ok = kk < a.K;
   const int kt = k_ok ? kk / a.C : 0, kc = k_ok ? kk - kt * a.C : 0;
-  const int tdy = a.tap_dy[kt], tdx = a.tap_dx[kt];
+  int tdy, tdx;
+  tap(kt, tdy, tdx);
   const int ohw = a.OH * a.OW;
 
   // Staging is branch-free: both operands are read through buffer descriptors, so a row past the pixel range, a column
@@ -393,6 +395,70 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgradArgs a) {
       }
 }
 
+template <typename T, int TILE, bool PSPLIT = false>
+__global__ __launch_bounds__(256) void wgrad16_kernel(const WgradArgs a) {
+  // XCD-aware order: hardware deals linear workgroup ids round-robin to the 8 XCDs; give each XCD a contiguous run of
+  // (split, tile) pairs so all tiles of one pixel split — which re-read the same dy / x rows — share one L2.
+  const int per_xcd = gridDim.x >> 3;
+  const int vid = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  if (vid >= a.total) return;
+  wgrad16_body<T, TILE, PSPLIT>(a, vid, [&](int kt, int& dy, int& dx) { dy = a.tap_dy[kt]; dx = a.tap_dx[kt]; });
+}
+
+// ------------------------------------------------------------------------------------------------ grouped launch (r05)
+// Several small-map problems in ONE launch of the 128-wide tile above.  A small-map layer alone has few dW tiles: filling the chip
+// takes many pixel splits (each ending in tile x tile atomics) or the 64-wide tile (twice the staged bytes per FLOP).  Together the
+// layers of a fork fill one resident round with 128-wide tiles and a few splits each.  Everything the kernel needs travels BY VALUE in
+// its argument block (no device table, no copy, no allocation: a captured graph replays the launch as it stands): a compact record
+// per problem plus the prefix sums of the workgroup counts.  A workgroup finds its problem by a wave-uniform scan of the prefix
+// sums, rebuilds that problem's WgradCore in scalar registers and runs the shared body; the tap offsets come from the filter
+// geometry (the two 64-byte tables of WgradArgs do not travel).
+struct WgradGroupProblem {          // 80 bytes
+  const void* x;
+  const void* dy;
+  float* dw;
+  int M, N, C;
+  int x_ld, dy_ld;
+  unsigned x_bytes, dy_bytes;
+  unsigned mag_ow, mag_oh;
+  int pix_per_split;
+  unsigned short IH, IW, OH, OW;
+  unsigned char sy, sx, KH, KW, DH, DW, PH, PW;
+};
+struct WgradGroupArgs {
+  int count, total;
+  int start[SY11_WGRAD_GROUP_MAX];              // first virtual workgroup id of problem i; entries past `count` hold INT_MAX
+  WgradGroupProblem p[SY11_WGRAD_GROUP_MAX];
+};
+static_assert(sizeof(WgradGroupProblem) == 80, "compact problem record");
+static_assert(sizeof(WgradGroupArgs) <= 4096, "the grouped launch's argument block must fit the 4 KB kernel-argument limit");
+
+template <typename T>
+__global__ __launch_bounds__(256) void wgrad16g_kernel(const WgradGroupArgs g) {
+  const int per_xcd = gridDim.x >> 3;
+  const int vid = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  if (vid >= g.total) return;
+  int pi = 0;                                   // wave-uniform: start[] is ascending, unused entries never compare true
+#pragma unroll
+  for (int i = 1; i < SY11_WGRAD_GROUP_MAX; ++i) pi += vid >= g.start[i] ? 1 : 0;
+  const WgradGroupProblem& q = g.p[pi];
+  WgradCore a;
+  a.x = q.x; a.dy = q.dy; a.dw = q.dw;
+  a.M = q.M; a.N = q.N; a.C = q.C; a.T = q.KH * q.KW; a.K = a.T * a.C;
+  a.x_ld = q.x_ld; a.dy_ld = q.dy_ld;
+  a.IH = q.IH; a.IW = q.IW; a.OH = q.OH; a.OW = q.OW; a.sy = q.sy; a.sx = q.sx;
+  a.tiles_k = (a.K + 127) >> 7;
+  a.x_bytes = q.x_bytes; a.dy_bytes = q.dy_bytes;
+  a.mag_ow = q.mag_ow; a.mag_oh = q.mag_oh;
+  a.tiles = a.tiles_k * ((a.N + 127) >> 7);
+  a.pix_per_split = q.pix_per_split;
+  a.dw_split_stride = 0;
+  const int kw = q.KW, dh = q.DH, dwd = q.DW, ph = q.PH, pw = q.PW;
+  wgrad16_body<T, 128, false>(a, vid - g.start[pi], [&](int kt, int& dy, int& dx) {
+    const int r = kt / kw, s = kt - r * kw;
+    dy = r * dh - ph; dx = s * dwd - pw;
+  });
+}
 
 // ------------------------------------------------------------------------------------------------ wide tile (r04)
 // wgrad16_kernel<128> is bound by the L2 -> LDS fill (r04 stamps: ~40-55 GB/s per CU whatever the schedule): 64 pixels x (128 + 128)
@@ -921,5 +987,102 @@ extern "C" int sy11_conv2d_wgrad(const sy11_conv_desc* d, const void* x, const v
     }
   }
   return wgrad_launch_cfg(a, d->dtype, st, cfg);
+}
+
+// ------------------------------------------------------------------------------------------------ grouped launch: host side
+// Work split of a group (pure arithmetic, exported so that it can be checked without a GPU).  Problem i has
+//     tiles_i = ceil(N_i / 128) * ceil(K_i / 128)  dW tiles   and   stages_i = ceil(M_i / 64)  stages of 64 pixels.
+// With G = target_workgroups:  chunk = max(8, ceil(sum_i tiles_i * stages_i / G))  stages,  splits_i = ceil(stages_i / chunk),
+// pix_per_split_i = 64 * ceil(stages_i / splits_i)  (the splits of one problem are balanced), and the problem owns the virtual
+// workgroup ids  wg_start[i] .. wg_start[i + 1]  =  wg_start[i] + tiles_i * ceil(M_i / pix_per_split_i),  split-major: id - wg_start[i]
+// = split * tiles_i + tile, so consecutive ids share a split (and, after the XCD remap, an L2).
+extern "C" int sy11_wgrad_group_plan(int32_t count, const int32_t* M, const int32_t* N, const int32_t* K, int32_t target_workgroups,
+                                     int32_t* pix_per_split, int32_t* wg_start) {
+  SY11_REQUIRE(M && N && K && pix_per_split && wg_start, "wgrad_group_plan: null argument");
+  SY11_REQUIRE(count >= 1 && count <= SY11_WGRAD_GROUP_MAX, "wgrad_group_plan: count %d outside 1..%d", count, SY11_WGRAD_GROUP_MAX);
+  SY11_REQUIRE(target_workgroups >= 1, "wgrad_group_plan: target_workgroups must be positive");
+  long work = 0;
+  for (int i = 0; i < count; ++i) {
+    SY11_REQUIRE(M[i] > 0 && N[i] > 0 && K[i] > 0, "wgrad_group_plan: problem %d: non-positive dims", i);
+    work += (long)cdiv(N[i], 128) * cdiv(K[i], 128) * cdiv(M[i], 64);
+  }
+  long chunk = (work + target_workgroups - 1) / target_workgroups;
+  if (chunk < 8) chunk = 8;
+  long at = 0;
+  for (int i = 0; i < count; ++i) {
+    const long tiles = (long)cdiv(N[i], 128) * cdiv(K[i], 128);
+    const int stages = cdiv(M[i], 64);
+    const int splits = cdiv(stages, chunk);
+    pix_per_split[i] = cdiv(stages, splits) * 64;
+    wg_start[i] = (int32_t)at;
+    at += tiles * cdiv(M[i], pix_per_split[i]);
+    SY11_REQUIRE(at < (1L << 30), "wgrad_group_plan: more than 2^30 workgroups");
+  }
+  wg_start[count] = (int32_t)at;
+  return SY11_OK;
+}
+
+extern "C" int sy11_conv2d_wgrad_group(int32_t dtype, int32_t count, const sy11_wgrad_problem* problems, int32_t target_workgroups,
+                                       void* stream) {
+  SY11_REQUIRE(problems, "conv2d_wgrad_group: null problem list");
+  SY11_REQUIRE(count >= 1 && count <= SY11_WGRAD_GROUP_MAX, "conv2d_wgrad_group: count %d outside 1..%d", count, SY11_WGRAD_GROUP_MAX);
+  SY11_REQUIRE(dtype_ok(dtype), "conv2d_wgrad_group: bad dtype");
+  if (dtype == SY11_F32) SY11_FAIL(SY11_EUNSUPPORTED, "conv2d_wgrad_group: 16-bit dtypes only (f32 problems go through conv2d_wgrad)");
+  SY11_REQUIRE(target_workgroups >= 0, "conv2d_wgrad_group: negative target_workgroups");
+  WgradGroupArgs g{};
+  int32_t Ms[SY11_WGRAD_GROUP_MAX], Ns[SY11_WGRAD_GROUP_MAX], Ks[SY11_WGRAD_GROUP_MAX], pps[SY11_WGRAD_GROUP_MAX], starts[SY11_WGRAD_GROUP_MAX + 1];
+  for (int i = 0; i < count; ++i) {
+    // the checks of sy11_conv2d_wgrad, per problem
+    const sy11_conv_desc* d = &problems[i].desc;
+    const void* x = problems[i].x;
+    const void* dy = problems[i].dy;
+    const int dy_ld = problems[i].dy_ld;
+    float* dw = problems[i].dw;
+    SY11_REQUIRE(x && dy && dw, "conv2d_wgrad_group: problem %d: null argument", i);
+    SY11_REQUIRE(d->dtype == dtype, "conv2d_wgrad_group: problem %d: dtype %d differs from the group's %d", i, d->dtype, dtype);
+    SY11_REQUIRE(d->B > 0 && d->IH > 0 && d->IW > 0 && d->C > 0 && d->N > 0 && d->KH > 0 && d->KW > 0, "conv2d_wgrad_group: problem %d: non-positive dims", i);
+    SY11_REQUIRE(d->SH > 0 && d->SW > 0 && d->DH > 0 && d->DW > 0 && d->PH >= 0 && d->PW >= 0, "conv2d_wgrad_group: problem %d: bad stride/dilation/pad", i);
+    SY11_REQUIRE(d->OH == (d->IH + 2 * d->PH - d->DH * (d->KH - 1) - 1) / d->SH + 1 && d->OW == (d->IW + 2 * d->PW - d->DW * (d->KW - 1) - 1) / d->SW + 1,
+                 "conv2d_wgrad_group: problem %d: OH/OW (%d,%d) do not match conv arithmetic", i, d->OH, d->OW);
+    SY11_REQUIRE(d->PH < 120 && d->DH * (d->KH - 1) < 120 && d->PW < 120 && d->DW * (d->KW - 1) < 120, "conv2d_wgrad_group: problem %d: tap offset exceeds int8", i);
+    if (d->groups != 1) SY11_FAIL(SY11_EUNSUPPORTED, "conv2d_wgrad_group: problem %d: groups=%d (dense problems only)", i, d->groups);
+    SY11_REQUIRE(d->KH * d->KW <= 64, "conv2d_wgrad_group: problem %d: <=64 taps", i);
+    SY11_REQUIRE(d->C % 8 == 0 && d->N % 8 == 0, "conv2d_wgrad_group: problem %d: C and N must be multiples of 8", i);
+    SY11_REQUIRE(d->x_ld % 8 == 0 && dy_ld % 8 == 0 && d->x_ld >= d->C && dy_ld >= d->N, "conv2d_wgrad_group: problem %d: bad pixel strides", i);
+    SY11_REQUIRE((((uintptr_t)x | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)dw & 3) == 0, "conv2d_wgrad_group: problem %d: misaligned pointer", i);
+    SY11_REQUIRE((long)d->B * d->IH * d->IW < (1L << 31) && (long)d->B * d->OH * d->OW < (1L << 31), "conv2d_wgrad_group: problem %d: pixel count overflows int32", i);
+    const long xb = ((long)d->B * d->IH * d->IW - 1) * d->x_ld * 2 + (long)d->C * 2;
+    const long db = ((long)d->B * d->OH * d->OW - 1) * dy_ld * 2 + (long)d->N * 2;
+    SY11_REQUIRE(xb < (1L << 31) && db < (1L << 31), "conv2d_wgrad_group: problem %d: operand view larger than 2 GiB", i);
+    SY11_REQUIRE((long)(d->OW + 64) * d->OW < (1L << 20) && (long)(d->OH + 64) * d->OH < (1L << 20), "conv2d_wgrad_group: problem %d: output map larger than 960 pixels per side", i);
+    // the compact record keeps the map sizes in 16 bits and the filter geometry in 8
+    SY11_REQUIRE(d->IH < 65536 && d->IW < 65536 && d->SH < 256 && d->SW < 256 && d->DH < 256 && d->DW < 256, "conv2d_wgrad_group: problem %d: geometry exceeds the compact record", i);
+    WgradGroupProblem& q = g.p[i];
+    q.x = x; q.dy = dy; q.dw = dw;
+    q.M = d->B * d->OH * d->OW; q.N = d->N; q.C = d->C;
+    q.x_ld = d->x_ld; q.dy_ld = dy_ld;
+    q.x_bytes = (unsigned)xb; q.dy_bytes = (unsigned)db;
+    q.mag_ow = (unsigned)(((1u << 20) + d->OW - 1) / d->OW);
+    q.mag_oh = (unsigned)(((1u << 20) + d->OH - 1) / d->OH);
+    q.IH = (unsigned short)d->IH; q.IW = (unsigned short)d->IW; q.OH = (unsigned short)d->OH; q.OW = (unsigned short)d->OW;
+    q.sy = (unsigned char)d->SH; q.sx = (unsigned char)d->SW; q.KH = (unsigned char)d->KH; q.KW = (unsigned char)d->KW;
+    q.DH = (unsigned char)d->DH; q.DW = (unsigned char)d->DW; q.PH = (unsigned char)d->PH; q.PW = (unsigned char)d->PW;
+    Ms[i] = q.M; Ns[i] = q.N; Ks[i] = d->KH * d->KW * d->C;
+  }
+  // ordered mode keeps one partial dW per split and folds them in order: that is the per-layer path's job
+  if (sy11_det(8)) SY11_FAIL(SY11_EUNSUPPORTED, "conv2d_wgrad_group: ordered reductions are on (use conv2d_wgrad per problem)");
+  const int G = target_workgroups > 0 ? target_workgroups : 2 * cu_count();      // one resident round of the 128-wide tile
+  const int rc = sy11_wgrad_group_plan(count, Ms, Ns, Ks, G, pps, starts);
+  if (rc) return rc;
+  g.count = count; g.total = starts[count];
+  for (int i = 0; i < SY11_WGRAD_GROUP_MAX; ++i) g.start[i] = i < count ? starts[i] : 0x7fffffff;
+  for (int i = 0; i < count; ++i) g.p[i].pix_per_split = pps[i];
+  sy11_note_cfg(1, SY11_CFG_WGRAD_GROUP);
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid(cdiv(g.total, 8) * 8), block(256);
+  if (dtype == SY11_F16) hipLaunchKernelGGL((wgrad16g_kernel<_Float16>), grid, block, 0, st, g);
+  else hipLaunchKernelGGL((wgrad16g_kernel<__bf16>), grid, block, 0, st, g);
+  SY11_LAUNCH_CHECK("conv2d_wgrad_group");
+  return SY11_OK;
 }
 

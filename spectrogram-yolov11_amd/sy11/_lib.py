@@ -26,6 +26,15 @@ class ConvDesc(C.Structure):
         "KH", "KW", "SH", "SW", "PH", "PW", "DH", "DW", "groups")] + [("flags", C.c_uint32), ("stat_slots", C.c_int32)]
 
 
+WGRAD_GROUP_MAX = 32          # SY11_WGRAD_GROUP_MAX
+CFG_WGRAD_GROUP = 100         # "wgrad_last_cfg" after a grouped launch (csrc/tune.h SY11_CFG_WGRAD_GROUP)
+
+
+class WgradProblem(C.Structure):
+    """sy11_wgrad_problem: one filter gradient of sy11_conv2d_wgrad_group (include/sy11.h)."""
+    _fields_ = [("desc", ConvDesc), ("x", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p), ("dy_ld", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BnTail(C.Structure):
     """sy11_bn_tail: BatchNorm finalisation folded into the producing conv's tail (include/sy11.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("gamma", "beta", "running_mean", "running_var", "mean", "rstd", "scale", "shift", "ticket")] \
@@ -78,6 +87,8 @@ SIGNATURES = {
     "sy11_stem_conv_fwd_bn": [_dp, _vp, _vp, _vp, _vp, _vp, _bp, _vp],
     "sy11_conv2d_dgrad": [_dp, _vp, _i32, _vp, _vp, _vp],
     "sy11_conv2d_wgrad": [_dp, _vp, _vp, _i32, _vp, _vp],
+    "sy11_conv2d_wgrad_group": [_i32, _i32, C.POINTER(WgradProblem), _i32, _vp],
+    "sy11_wgrad_group_plan": [_i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_i32)],
     "sy11_weight_transpose": [_i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "sy11_weight_transpose_multi": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "sy11_stem_conv_fwd": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -111,6 +111,49 @@ _SIDE_BATCH = max(int(os.environ.get("SY11_WGRAD_STREAM", "32") or 0), 1)
 # small maps, where neither kernel fills the chip.  An EARLIER first fork — 12 / 20 / 8 launches, then 32 / 40 / 36 — also loses:
 # 19.72 / 19.74 / 20.06 ms against 19.57-19.59.)
 _SIDE_STREAMS = {}
+# The small-map filter gradients of one fork in ONE launch (ops.conv2d_wgrad_group, csrc/wgrad.hip wgrad16g_kernel): a small-map layer
+# alone has too few dW tiles to fill the chip without many pixel splits (each ending in tile x tile atomics) or the 64-wide tile.
+# SY11_WGRAD_GROUP=0 keeps one launch per layer; so do ordered reductions and SY11_WGRAD_STREAM=0 (no fork, nothing to group).
+_WGRAD_GROUP = os.environ.get("SY11_WGRAD_GROUP", "1") != "0"
+_PER_LAYER_WGRAD = ops.conv2d_wgrad             # what a grouped launch stands in for (see flush_side)
+# "Small": M = B * OH * OW <= 32768, the 20x20 maps of a 640^2 batch of 64 and the stride-2 layers that end there.  r05, same box, five
+# alternating runs: 19.37 ms grouping off, 19.10 with M <= 25600 (range 0.11), 19.12 with M <= 131072 (range 0.20): the 40x40 layers
+# gain 0.18 ms of kernel time alone in a graph (tools/wgrad_group_micro.py) and nothing in the step, where their per-layer
+# launches (half of them the patch kernel) already overlap the BatchNorm passes.
+_WGRAD_GROUP_MAX_PIXELS = int(os.environ.get("SY11_WGRAD_GROUP_M", "32768") or 0)
+# Workgroups per grouped launch: three per CU, i.e. one and a half resident rounds of the 128-wide tile (r05, same box, the 34 layers
+# of the 20x20 maps as two launches: 0.69 / 0.59 / 0.63 / 0.62 / 0.61 ms at 2 / 3 / 4 / 6 / 8 per CU, 0.95-1.0 ms one launch per layer;
+# headline 19.22 ms at 2 per CU, 19.12 at 3).  One round exactly leaves a partial second round of full-length workgroups behind —
+# the split rounds each problem's share UP; shorter workgroups even that out, more of them only add atomics.
+_WGRAD_GROUP_TARGET = int(os.environ.get("SY11_WGRAD_GROUP_WG", "0") or 0)              # 0 = 3 x the device's CU count
+_GROUP_TARGETS = {}
+
+
+def _wgrad_group_target(device):
+    if _WGRAD_GROUP_TARGET > 0:
+        return _WGRAD_GROUP_TARGET
+    d = torch.device(device)
+    key = d.index if d.index is not None else torch.cuda.current_device()
+    if key not in _GROUP_TARGETS:
+        _GROUP_TARGETS[key] = 3 * torch.cuda.get_device_properties(key).multi_processor_count
+    return _GROUP_TARGETS[key]
+
+
+def _wgrad_is_small(problem):
+    """A filter gradient joins the grouped launch when its output map has at most _WGRAD_GROUP_MAX_PIXELS pixels (batch included)."""
+    dy = problem[1]
+    return dy.shape[0] * dy.shape[1] * dy.shape[2] <= _WGRAD_GROUP_MAX_PIXELS
+
+
+class _GroupedWgrad:
+    """A queued filter gradient that may go out in a grouped launch: calling it runs the per-layer closure."""
+    __slots__ = ("fn", "problem")
+
+    def __init__(self, fn, problem):
+        self.fn, self.problem = fn, problem
+
+    def __call__(self):
+        self.fn()
 
 
 def _side_stream(device):
@@ -204,15 +247,19 @@ class Ctx:
         self.main_stream = None           # the stream a branch section was entered from (set while any branch is open)
         self.tape_branches: List = []     # (first tape index, end, branch) of the closures recorded inside a branch section
 
-    def on_side(self, fn, *keep):
+    def on_side(self, fn, *keep, wgrad=None):
         """Run ``fn`` (kernel launches) on the side stream, ordered after everything issued so far on the current stream.
-        ``keep``: tensors the side work reads — held until join_side() so the allocator cannot recycle them early."""
+        ``keep``: tensors the side work reads — held until join_side() so the allocator cannot recycle them early.
+        ``wgrad``: when ``fn`` is a plain dense 16-bit filter gradient, its (x, dy, dw, k, s, p, d): flush_side() may then issue it
+        in a grouped launch with its neighbours instead of calling ``fn``."""
         if not self.use_side:
             fn()
             return
         if self.side is None:
             self.side = _side_stream(self.device)
             self.side_queue = []
+        if wgrad is not None and _WGRAD_GROUP and _wgrad_is_small(wgrad):
+            fn = _GroupedWgrad(fn, wgrad)
         self.side_queue.append(fn)
         self.side_refs.append(keep)
         if len(self.side_queue) >= _SIDE_BATCH:
@@ -234,8 +281,17 @@ class Ctx:
             if st != cur:
                 self.side.wait_stream(st)
         with torch.cuda.stream(self.side):
+            # the small-map filter gradients of the batch first, in grouped launches — unless ordered reductions are on (the
+            # grouped kernel adds with atomics), or ops.conv2d_wgrad has been replaced (a per-launch audit or timer hooked onto it:
+            # a grouped launch would bypass the hook): every closure then runs as it always did
+            group = [fn for fn in self.side_queue if isinstance(fn, _GroupedWgrad)]
+            if len(group) >= 2 and ops._lib.get_option("deterministic") == 0 and ops.conv2d_wgrad is _PER_LAYER_WGRAD:
+                ops.conv2d_wgrad_group([fn.problem for fn in group], _wgrad_group_target(self.device))
+            else:
+                group = []
             for fn in self.side_queue:
-                fn()
+                if not (group and isinstance(fn, _GroupedWgrad)):
+                    fn()
         self.side_queue = []
 
     def branch(self, b):

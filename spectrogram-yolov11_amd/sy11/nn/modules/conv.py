@@ -239,7 +239,9 @@ class Conv(nn.Module):
                         dw.add_(dwp[..., :C1])
                     else:
                         xd = x.data
-                        ec.on_side(lambda: ops.conv2d_wgrad(xd, dy, dw, k, s, p, d, g), xd, dy)
+                        plain = g == 1 and ec.dtype in (torch.float16, torch.bfloat16)      # may join a grouped launch
+                        ec.on_side(lambda: ops.conv2d_wgrad(xd, dy, dw, k, s, p, d, g), xd, dy,
+                                   wgrad=(xd, dy, dw, k, s, p, d) if plain else None)
                 if padded and x_real.req:
                     gp = torch.zeros_like(x.data)
                     ops.conv2d_dgrad(dy, ops.weight_transpose(w), gp, (B, OH, OW, N), k, s, p, d, 1, accumulate=True)

@@ -158,6 +158,43 @@ def conv2d_wgrad(x, dy, dw_f32, k, s=1, p=0, d=1, groups=1):
     return dw_f32
 
 
+def conv2d_wgrad_group(problems, target_workgroups=0):
+    """Several dense 16-bit filter gradients in one launch (sy11_conv2d_wgrad_group): ``problems`` is a sequence of
+    (x, dy, dw_f32, k, s, p, d), each exactly conv2d_wgrad(x, dy, dw_f32, k, s, p, d).  A list longer than WGRAD_GROUP_MAX goes out
+    as several launches.  ``target_workgroups``: workgroups per launch, 0 = one resident round of the chip."""
+    problems = list(problems)
+    if not problems:
+        raise _lib.Sy11Error("conv2d_wgrad_group: empty problem list")
+    dt = problems[0][0].dtype
+    for at in range(0, len(problems), _lib.WGRAD_GROUP_MAX):
+        part = problems[at:at + _lib.WGRAD_GROUP_MAX]
+        arr = (_lib.WgradProblem * len(part))()
+        flops = nbytes = 0.0
+        for i, (x, dy, dw, k, s, p, d) in enumerate(part):
+            _need_gpu(x, dy, dw)
+            if dw.dtype != torch.float32 or not dw.is_contiguous():
+                raise _lib.Sy11Error("conv2d_wgrad_group: dw must be a contiguous f32 tensor")
+            if x.dtype != dt or dy.dtype != dt:
+                raise _lib.Sy11Error("conv2d_wgrad_group: every problem of a group has the same dtype")
+            arr[i].desc = _desc(x.shape, view_ld(x), dy.shape, view_ld(dy), x.dtype, k, s, p, d, 1, 0)
+            arr[i].x, arr[i].dy, arr[i].dw, arr[i].dy_ld = x.data_ptr(), dy.data_ptr(), dw.data_ptr(), view_ld(dy)
+            if _lib.PROFILE is not None:
+                flops += _lib.PROFILE_META["flops"]
+                nbytes += _lib.PROFILE_META["bytes"]
+        if _lib.PROFILE is not None:
+            _lib.PROFILE_META = {"flops": flops, "groups": 1, "bytes": nbytes, "desc": f"group of {len(part)}"}
+        call("sy11_conv2d_wgrad_group", dt_code(dt), len(part), arr, int(target_workgroups), _stream())
+
+
+def wgrad_group_plan(M, N, K, target_workgroups):
+    """The work split of one grouped launch (sy11_wgrad_group_plan, host arithmetic): (pix_per_split[count], wg_start[count + 1])."""
+    n = len(M)
+    arr = lambda v: (C.c_int32 * max(len(v), 1))(*[int(e) for e in v])
+    pps, start = (C.c_int32 * max(n, 1))(), (C.c_int32 * (n + 1))()
+    _lib.check(_lib.load().sy11_wgrad_group_plan(n, arr(M), arr(N), arr(K), int(target_workgroups), pps, start), "sy11_wgrad_group_plan")
+    return list(pps)[:n], list(start)
+
+
 def stem_conv_fwd(x_nchw, w_krsc, y, s=2, p=1, bias=None, stats=None, silu=False):
     _need_gpu(x_nchw, w_krsc, y)
     if x_nchw.dtype != torch.float32 or not x_nchw.is_contiguous() or x_nchw.shape[1] != 3:

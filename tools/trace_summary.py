@@ -51,6 +51,8 @@ def short(k):
 
 
 def family(k):
+    if "wgrad16g_kernel" in k:                       # the grouped launch of the small-map layers: the same family as its per-layer form
+        return "conv wgrad (dense)"
     for fam, spec in FAMILIES.items():
         if any(s in k for s in spec["symbols"]):
             return fam
