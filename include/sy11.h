@@ -962,6 +962,55 @@ int sy11_rs_decode(int32_t n_frame, const int32_t* row_host, const int32_t* row,
 int sy11_rs_check(int32_t n_frame, const int32_t* row_host, const int32_t* row, const sy11_rs_code* code, const sy11_fec_crc* crc, int64_t n_rows,
                   int64_t stride_info, const uint8_t* info, const int32_t* cw, int32_t* rows, void* stream);
 
+/* ---- LDPC frame decoding: the layered normalised min-sum decoder of a quasi-cyclic LDPC code, de-whitening and CRC (spec in DESIGN.md §4) ----
+ * Three launches over all frames (sy11/data/ldpc.py).  Launch 1 is sy11_fec_soft, unchanged, with T = N / 2, tail 0, period 2, pattern 3: it
+ * writes the N int8 soft bits y of a frame, y > 0 = bit 0, 0 = an erasure.  Launches 2 and 3 take the frames as a table of int32 rows, as the
+ * Reed-Solomon launches do: frame i reads row row[i] of soft (n_rows, stride_soft) int8 and writes that row of bits (n_rows, stride_bits) uint8,
+ * out (n_rows, 2) int32, post (n_rows, stride_post) int16, data (n_rows, stride_data) uint8 and rows (n_rows, 5) int32.  row: DEVICE, row_host:
+ * its HOST copy; every row inside the tables and named once.  Exact integer arithmetic; no atomics; a frame's result does not depend on the
+ * others.  Nothing is launched and nothing written on an error.
+ *
+ * The code: an mb x nb base matrix over Z x Z circulants, 1 <= mb <= 64, mb < nb <= 128, 1 <= Z <= 512, N = nb Z even and at most N_MAX = 16384
+ * (what launch 1 can write; the value of sy11_ldpc_nmax), M = mb Z, K = N - M; systematic: the first K bits of a codeword are the information.
+ * Layer i holds the entries layer[i] .. layer[i + 1] of the entry table, 2 .. 32 of them, each a (column, shift) with column in [0, nb), no column
+ * twice in a layer, and shift in [0, Z); layer[0] = 0, layer[mb] = n_entry; every column has an entry.  Entry j of layer i joins check
+ * c = i Z + r to variable n_j = column Z + (r + shift) mod Z, r in [0, Z).  layer, entry: DEVICE; layer_host, entry_host: their HOST copies,
+ * checked entry by entry before the launch.  sy11_ldpc_lds_bytes: the dynamic LDS the code takes, 2 N + 8 M + 4 n_entry + 4 (mb + 1) + 16 with
+ * each part rounded up to 16 (-1 for a Z, mb, nb or n_entry outside the limits); a code that takes more than 160 KiB is refused.
+ *
+ * Launch 2, sy11_ldpc_decode.  Q[n] = y[n], R[c, j] = 0.  Iteration it = 1 .. iterations (1 .. 100), layer i = 0 .. mb - 1 in order, every check
+ * c of the layer: T_j = Q[n_j] - R[c, j], s_j = T_j < 0, a_j = |T_j|; m1 = min_j a_j at j1 (any j attaining it), m2 = min over j != j1, S = XOR_j
+ * s_j; R[c, j] = (S ^ s_j ? -1 : +1) min((scale (j == j1 ? m2 : m1)) >> 4, 127), Q[n_j] = T_j + R[c, j]; scale in [1, 16], sixteenths.  After the
+ * mb layers x[n] = Q[n] < 0, unsat = #{c : XOR_j x[n_j] = 1}; the frame stops at unsat = 0.  |Q| <= 127 * 65: int16 holds it unclamped.
+ * bits[row stride_bits ...] = x packed MSB first, zeros after the N bits to the end of the row; out[2 row + 0 .. 1] = iterations run, unsat;
+ * post[row stride_post + n] = Q[n], n in [0, N) (post may be null; stride_post counts int16; what follows the N values is not written).  One
+ * workgroup per frame, 64 threads per started 64 checks of a layer, 256 at the most.
+ *
+ * Launch 3, sy11_ldpc_check.  n_channel = #{n : y[n] != 0}, channel_errors = #{n : y[n] != 0 and (y[n] < 0) != x[n]}.  v_t = x_t ^ whiten[t],
+ * t < K (whiten: DEVICE, K bytes of 0 / 1, or null); data[row stride_data ...] = v packed MSB first, zeros after them.  crc: HOST, the Rocksoft
+ * model of sy11_fec_crc with the semantics of sy11_fec_check: width 0 = none, else 8 .. 32 and K > width; crc_recv = the last `width` bits of v,
+ * crc_calc over the K - width bits before them.  rows[5 row + 0 .. 4] = crc_calc, crc_recv, crc_ok (1 / 0, -1 without a crc), channel_errors,
+ * n_channel.  Checked too: N even in [2, N_MAX], 1 <= K < N, the strides.                                                              */
+typedef struct sy11_ldpc_code {
+  int32_t Z;                   /* the circulants' size, 1 .. 512                                                    */
+  int32_t mb;                  /* block rows (layers), 1 .. 64                                                      */
+  int32_t nb;                  /* block columns, mb + 1 .. 128, nb Z even and at most N_MAX                         */
+  int32_t n_entry;             /* entries of the base matrix that are not -1                                        */
+} sy11_ldpc_code;
+typedef struct sy11_ldpc_entry {
+  int32_t column;              /* block column, 0 .. nb - 1                                                         */
+  int32_t shift;               /* row r of the block has its one in column (r + shift) mod Z, 0 .. Z - 1            */
+} sy11_ldpc_entry;
+int32_t sy11_ldpc_nmax(void);                     /* N_MAX: the bits of a codeword at the most, a constant of the build */
+int64_t sy11_ldpc_lds_bytes(int32_t Z, int32_t mb, int32_t nb, int32_t n_entry);
+int sy11_ldpc_decode(int32_t n_frame, const int32_t* row_host, const int32_t* row, const sy11_ldpc_code* code, const int32_t* layer_host,
+                     const int32_t* layer, const sy11_ldpc_entry* entry_host, const sy11_ldpc_entry* entry, int32_t iterations, int32_t scale,
+                     int64_t n_rows, int64_t stride_soft, const int8_t* soft, int64_t stride_bits, uint8_t* bits, int32_t* out,
+                     int64_t stride_post, int16_t* post, void* stream);
+int sy11_ldpc_check(int32_t n_frame, const int32_t* row_host, const int32_t* row, int32_t N, int32_t K, const uint8_t* whiten,
+                    const sy11_fec_crc* crc, int64_t n_rows, int64_t stride_soft, const int8_t* soft, int64_t stride_bits, const uint8_t* bits,
+                    int64_t stride_data, uint8_t* data, int32_t* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

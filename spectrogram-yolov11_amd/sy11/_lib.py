@@ -75,6 +75,11 @@ class RsCode(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n", "k", "fcr", "prim", "interleave", "poly")]
 
 
+class LdpcCode(C.Structure):
+    """sy11_ldpc_code: the size of a quasi-cyclic LDPC code's base matrix and circulants for sy11_ldpc_decode (include/sy11.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("Z", "mb", "nb", "n_entry")]
+
+
 _vp, _i32, _i64, _f32, _f64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32, C.c_uint64
 _dp = C.POINTER(ConvDesc)
 _bp = C.POINTER(BnTail)
@@ -162,6 +167,8 @@ SIGNATURES = {
     "sy11_fec_check": [_i32, _vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(FecCrc), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_rs_decode": [_i32, _vp, _vp, C.POINTER(RsCode), _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_rs_check": [_i32, _vp, _vp, C.POINTER(RsCode), C.POINTER(FecCrc), _i64, _i64, _vp, _vp, _vp, _vp],
+    "sy11_ldpc_decode": [_i32, _vp, _vp, C.POINTER(LdpcCode), _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "sy11_ldpc_check": [_i32, _vp, _vp, _i32, _i32, _vp, C.POINTER(FecCrc), _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
 }
 SIGNATURES.update({
     "sy11_set_option": [C.c_char_p, _i32],
@@ -188,6 +195,8 @@ OTHER = {"sy11_version": ([], C.c_int), "sy11_last_error": ([], C.c_char_p),
          "sy11_sync_tile": ([], C.c_int32),
          "sy11_eq_tile": ([], C.c_int32),
          "sy11_fec_tmax": ([], C.c_int32),
+         "sy11_ldpc_nmax": ([], C.c_int32),
+         "sy11_ldpc_lds_bytes": ([_i32, _i32, _i32, _i32], C.c_int64),
          "sy11_tune_export": ([_vp, _i64], C.c_int64)}
 
 _lib = None

@@ -387,6 +387,13 @@ class YOLO:
         from ..data.decode import decode_frames
         return decode_frames(frames, demodulation, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
 
+    def decode_ldpc(self, frames, demodulation, *, code, iterations=20, scale=12, whiten=None, crc=None, soft_scale=16.0):
+        """Decode every frame of ``frames`` (found in ``demodulation``) as a codeword of the quasi-cyclic LDPC code ``code`` on the GPU -> ``sy11.data.ldpc.LdpcDecoded``:
+        per frame the de-whitened information bits of the layered min-sum decoder, the iterations it ran, whether every check is satisfied, the channel bit
+        errors against the decision and whether the CRC holds (``DetectionPredictor.decode_ldpc``)."""
+        from ..data.ldpc import decode_ldpc_frames
+        return decode_ldpc_frames(frames, demodulation, code=code, iterations=iterations, scale=scale, whiten=whiten, crc=crc, soft_scale=soft_scale)
+
     def correct(self, decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=None):
         """Correct every frame of ``decoded`` with the Reed-Solomon outer code on the GPU -> ``sy11.data.correct.Corrected``: per frame the information bytes of
         its ``interleave`` de-interleaved codewords, the byte errors corrected in each (-1: beyond the code) and whether the CRC over them holds

@@ -350,6 +350,24 @@ class DetectionPredictor:
         from ..data.decode import decode_frames
         return decode_frames(frames, demodulation, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
 
+    def decode_ldpc(self, frames, demodulation, *, code, iterations=20, scale=12, whiten=None, crc=None, soft_scale=16.0):
+        """Turn the channel bits of every frame of ``frames`` (what ``find_frames`` returned for ``demodulation``) into a checked message when the frames are
+        block-coded with a quasi-cyclic LDPC code -> ``sy11.data.ldpc.LdpcDecoded``, one row per frame in the frames' order (``csrc/ldpc.hip``).  ``code``: an
+        ``LdpcCode`` (``sy11.data.ldpc.ldpc_code`` of a standard's base matrix typed in, or the seeded test code ``ldpc_staircase``) or a dict ``{"Z": ..., "base": ...}``
+        with -1 for an empty block and the circulant's shift otherwise; N = nb Z received bits carry K = N - mb Z information bits, the first K of the
+        codeword, whitened by the 0/1 sequence ``whiten`` (``sy11.data.decode.lfsr_bits``) and protected by ``crc`` (a name of ``sy11.data.decode.CRCS`` or a Rocksoft
+        dict), the check field their last bits.  All frames go through THREE launches: the payload symbols turned back by the frame's rotation, scaled so
+        that a clean component is ``soft_scale`` and quantised to int8 (the first launch of ``decode``, unchanged); the layered normalised min-sum decoder,
+        one workgroup per frame with the posteriors in LDS, at most ``iterations`` sweeps with the check messages scaled by ``scale`` sixteenths, in exact
+        integer arithmetic, a frame stopping at the first sweep that satisfies every check (``iterations``, ``unsatisfied``, ``converged``); and the decision
+        compared with the received signs (``channel_errors`` of ``n_channel``, ``ber``), the information bits de-whitened and packed on the device
+        (``LdpcDecoded.bits(k)``, ``message(k)``, ``posterior(k)``) and their CRC (``crc_ok``).  ``find_frames`` must have read ``payload`` symbols enough for the N
+        bits; a frame cut short by the clip's end is a row with ``valid`` False and the reason "short", one of a clip without a positive gain has the reason
+        "gain".  The result goes on to ``correct`` as a ``Decoded`` does.  Shortened or punctured codes and named presets are out of scope.  Argument errors
+        are ``ValueError``s raised before anything touches the device; without a valid frame nothing is launched."""
+        from ..data.ldpc import decode_ldpc_frames
+        return decode_ldpc_frames(frames, demodulation, code=code, iterations=iterations, scale=scale, whiten=whiten, crc=crc, soft_scale=soft_scale)
+
     def correct(self, decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=None):
         """Remove the byte errors the Viterbi decoder left in every frame of ``decoded`` (what ``decode`` returned) with the Reed-Solomon outer code ->
         ``sy11.data.correct.Corrected``, one row per frame in the frames' order (``csrc/rs.hip``).  ``code``: a name of ``sy11.data.correct.CODES``

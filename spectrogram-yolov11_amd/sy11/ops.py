@@ -1646,6 +1646,106 @@ def rs_check(info, cw, frames, code, rows, interleave=1, crc=None):
     return rows
 
 
+def _ldpc_rows(what, frames, n_rows):
+    """The rows the frames read, each inside the tables and named once -> the contiguous int32 table."""
+    fr = np.asarray(frames)
+    if fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31 or not np.issubdtype(fr.dtype, np.integer):
+        raise ValueError(f"{what}: `frames` must be a non-empty 1-D integer array of the rows the frames read")
+    row = fr.astype(np.int64)
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        i = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise ValueError(f"{what}: frame {i} reads row {int(row[i])} of a table of {n_rows} rows (a row takes one frame)")
+    return np.ascontiguousarray(row.astype(np.int32))
+
+
+def _ldpc_call(name, *args):
+    """The library's refusal as a ``ValueError``, as this file's own."""
+    try:
+        call(name, *args)
+    except _lib.Sy11Error as e:
+        raise ValueError(str(e)) from None
+
+
+def ldpc_decode(soft, frames, code, bits, out, post=None, iterations=20, scale=12):
+    """Launch 2 of the LDPC frame decoder (sy11_ldpc_decode): the layered normalised min-sum decoder of ``code`` (a ``sy11.data.ldpc.LdpcCode`` or a dict Z, base) over
+    the N int8 soft bits ``soft[row]`` (rows, stride) of every frame of ``frames`` (the rows they read, a 1-D integer array), at most ``iterations`` sweeps (1 .. 100) with
+    the check messages scaled by ``scale`` sixteenths (1 .. 16); a frame stops at the first sweep whose decision satisfies every check.  ``bits[row]`` (rows, stride)
+    uint8 takes the N decided bits packed MSB first, zero-padded to the stride, ``out[row]`` (rows, 2) int32 the iterations run and the checks left unsatisfied, and
+    ``post[row]`` (rows, stride >= N) int16, if given, the final values Q.  One workgroup per frame, exact integer arithmetic.  A refused call raises ``ValueError`` and
+    writes nothing.  -> ``(bits, out, post)``."""
+    from .data.ldpc import _code_of
+    what = "ldpc_decode"
+    n_max = _lib.load().sy11_ldpc_nmax()
+    cd = _code_of(what, code)
+    _rs_table(what, "soft", soft, torch.int8, None, least=cd.N)
+    dev, n_rows = soft.device, soft.shape[0]
+    _rs_table(what, "bits", bits, torch.uint8, dev, n_rows=n_rows, least=(cd.N + 7) // 8)
+    _rs_table(what, "out", out, torch.int32, dev, n_rows=n_rows, shape=(2,))
+    if post is not None:
+        _rs_table(what, "post", post, torch.int16, dev, n_rows=n_rows, least=cd.N)
+    if soft.shape[1] > n_max or bits.shape[1] > n_max // 8 or (post is not None and post.shape[1] > n_max):
+        raise ValueError(f"{what}: a row of `soft` / `post` holds at most {n_max} values and one of `bits` {n_max // 8} bytes")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))     # noqa: E731
+    if not is_int(iterations) or not 1 <= iterations <= 100:
+        raise ValueError(f"{what}: iterations {iterations!r} is not an integer in [1, 100]")
+    if not is_int(scale) or not 1 <= scale <= 16:
+        raise ValueError(f"{what}: scale {scale!r} is not an integer in [1, 16] (sixteenths)")
+    row = _ldpc_rows(what, frames, n_rows)
+    # one upload: the frames' rows, the layers' offsets, the entries
+    layer, entry = np.ascontiguousarray(cd.layer, dtype=np.int32), np.ascontiguousarray(cd.entry)
+    host = np.concatenate((row, layer, entry.view(np.int32)))
+    t = torch.from_numpy(host).to(dev)
+    o1, o2 = row.shape[0], row.shape[0] + layer.shape[0]
+    spec = _lib.LdpcCode(cd.Z, cd.mb, cd.nb, entry.shape[0])
+    _ldpc_call("sy11_ldpc_decode", row.shape[0], C.c_void_p(row.ctypes.data), C.c_void_p(t.data_ptr()), C.byref(spec), C.c_void_p(layer.ctypes.data),
+               C.c_void_p(t.data_ptr() + 4 * o1), C.c_void_p(entry.ctypes.data), C.c_void_p(t.data_ptr() + 4 * o2), int(iterations), int(scale), n_rows, soft.shape[1], _p(soft),
+               bits.shape[1], _p(bits), _p(out), 0 if post is None else post.shape[1], _p(post), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return bits, out, post
+
+
+def ldpc_check(soft, bits, frames, N, K, data, rows, whiten=None, crc=None):
+    """Launch 3 of the LDPC frame decoder (sy11_ldpc_check): for every frame of ``frames`` the ``N`` decided bits ``bits[row]`` are compared with the signs of ``soft[row]`` where
+    it is not 0; the first ``K`` of them, XORed with ``whiten`` (a uint8 device vector of ``K`` 0/1, or None), are written packed MSB first, zero-padded, to ``data[row]`` (rows,
+    stride) uint8, and (crc_calc, crc_recv, crc_ok, channel_errors, n_channel) to ``rows[row]`` (rows, 5) int32; ``crc``: None (crc_ok = -1) or a dict width / poly / init /
+    refin / refout / xorout (``sy11.data.decode.CRCS``), the check field the last bits of the K.  A refused call raises ``ValueError`` and writes nothing.
+    -> ``(data, rows)``."""
+    what = "ldpc_check"
+    n_max = _lib.load().sy11_ldpc_nmax()
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))     # noqa: E731
+    if not is_int(N) or not is_int(K) or not 2 <= N <= n_max or N % 2 or not 1 <= K < N:
+        raise ValueError(f"{what}: N = {N!r} is not an even integer in [2, {n_max}], or K = {K!r} not an integer in [1, N)")
+    N, K = int(N), int(K)
+    _rs_table(what, "soft", soft, torch.int8, None, least=N)
+    dev, n_rows = soft.device, soft.shape[0]
+    _rs_table(what, "bits", bits, torch.uint8, dev, n_rows=n_rows, least=(N + 7) // 8)
+    _rs_table(what, "data", data, torch.uint8, dev, n_rows=n_rows, least=(K + 7) // 8)
+    _rs_table(what, "rows", rows, torch.int32, dev, n_rows=n_rows, shape=(5,))
+    if soft.shape[1] > n_max or bits.shape[1] > n_max // 8 or data.shape[1] > n_max // 8:
+        raise ValueError(f"{what}: a row of `soft` holds at most {n_max} values and one of `bits` / `data` {n_max // 8} bytes")
+    if whiten is not None:
+        try:
+            _u8_vector(what, "whiten", whiten, dev, K)
+        except _lib.Sy11Error as e:
+            raise ValueError(str(e)) from None
+    spec = _lib.FecCrc()
+    if crc is not None:
+        try:
+            W, poly, init, xorout, refin, refout = (int(crc[k]) for k in ("width", "poly", "init", "xorout", "refin", "refout"))
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
+        if not 8 <= W <= 32 or K <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) or refout not in (0, 1) or (refin and (K - W) % 8):
+            raise ValueError(f"{what}: the crc {crc!r} is not of 8 .. 32 bits below K = {K}, with fields of that width (and whole bytes with refin)")
+        spec = _lib.FecCrc(W, poly, init, xorout, refin, refout)
+    row = _ldpc_rows(what, frames, n_rows)
+    t = torch.from_numpy(row).to(dev)
+    _ldpc_call("sy11_ldpc_check", row.shape[0], C.c_void_p(row.ctypes.data), _p(t), N, K, _p(whiten), C.byref(spec), n_rows, soft.shape[1], _p(soft), bits.shape[1], _p(bits),
+               data.shape[1], _p(data), _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(dev))
+    return data, rows
+
+
 SCAN_METRICS = {"iou": 0, "ios": 1}
 
 
