@@ -21,8 +21,10 @@
 //  * The traceback is SERIAL per frame: T dependent steps.  A lane loads the survivor words of 64 steps with one ds_read_b64, the chain
 //    then runs on v_readlane and shifts, without an LDS round trip per step; every lane walks the same path, and lanes 0 .. 7 write the 8
 //    bytes of each 64 decided bits.
-//  * Launches 1 and 3 are bandwidth-trivial: one workgroup of 256 per frame; the CRC is a serial bit loop of one thread (at most 8192 bits).
+//  * Launches 1 and 3 are bandwidth-trivial: one workgroup of 256 per frame; the CRC is a serial bit loop of one thread (at most 8192 bits).  What
+//    launch 3 shares with the check launches of ldpc.hip and rs.hip (the de-whitened bytes, the CRC, the result row, the CRC's refusals) is frame_check.h.
 #include "common.h"
+#include "frame_check.h"
 
 #include <math.h>
 
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256) void fec_check_kernel(const sy11_fec_frame* __
   __shared__ uint8_t ub[FEC_TMAX / 8], vb[FEC_TMAX / 8];
   __shared__ int sh[2][4];
   const sy11_fec_frame f = frames[blockIdx.x];
-  const int t = threadIdx.x, T = f.T, n_bytes = (T + 7) / 8, n_data = (n_info + 7) / 8;
+  const int t = threadIdx.x, T = f.T, n_bytes = (T + 7) / 8;
   const uint8_t* src = bits + (int64_t)f.row * stride_bits;
   for (int b = t; b < n_bytes; b += 256) ub[b] = src[b];
   __syncthreads();
@@ -144,53 +146,13 @@ __global__ __launch_bounds__(256) void fec_check_kernel(const sy11_fec_frame* __
     n_ch += (y0 != 0) + (y1 != 0);
     n_err += (y0 != 0 && (y0 < 0) != fec_parity(R & g0)) + (y1 != 0 && (y1 < 0) != fec_parity(R & g1));
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) n_ch += __shfl_xor(n_ch, d), n_err += __shfl_xor(n_err, d);
-  if ((t & 63) == 0) sh[0][t >> 6] = n_ch, sh[1][t >> 6] = n_err;
-  // the information bits, de-whitened, packed MSB first; zeros after them
-  uint8_t* dst = data + (int64_t)f.row * stride_data;
-  for (int64_t b = t; b < stride_data; b += 256) {
-    int byte = 0;
-    if (b < n_data) {
-      byte = ub[b];
-      for (int i = 0; i < 8; ++i) {
-        const int at = (int)b * 8 + i;
-        if (at >= n_info) byte &= ~(0x80 >> i);
-        else if (whiten) byte ^= (whiten[at] & 1) << (7 - i);
-      }
-      vb[b] = (uint8_t)byte;
-    }
-    dst[b] = (uint8_t)byte;
-  }
+  frame_count_reduce(n_ch, n_err, sh, t);
+  frame_dewhiten_pack(ub, n_info, whiten, stride_data, data + (int64_t)f.row * stride_data, vb, t);
   __syncthreads();
   if (t != 0) return;
-  int32_t* o = rows + (int64_t)f.row * 5;
-  uint32_t calc = 0, recv = 0;
-  int ok = -1;
-  if (crc.width) {
-    const int W = crc.width, n_msg = n_info - W;
-    const uint64_t top = 1ull << (W - 1), all = (top << 1) - 1ull;
-    uint64_t reg = crc.init & all;
-    for (int k = 0; k < n_msg; ++k) {
-      const int at = crc.refin ? (k & ~7) | (7 - (k & 7)) : k;             // with refin each group of 8 bits is taken LSB first
-      const uint64_t bit = (vb[at >> 3] >> (7 - (at & 7))) & 1;
-      const uint64_t fb = ((reg >> (W - 1)) & 1ull) ^ bit;
-      reg = (reg << 1) & all;
-      if (fb) reg ^= crc.poly;
-    }
-    if (crc.refout) {
-      uint64_t r = 0;
-      for (int i = 0; i < W; ++i) r |= ((reg >> i) & 1ull) << (W - 1 - i);
-      reg = r;
-    }
-    calc = (uint32_t)((reg ^ crc.xorout) & all);
-    uint64_t got = 0;
-    for (int k = n_msg; k < n_info; ++k) got = (got << 1) | ((vb[k >> 3] >> (7 - (k & 7))) & 1);
-    recv = (uint32_t)got;
-    ok = calc == recv;
-  }
-  o[0] = (int32_t)calc, o[1] = (int32_t)recv, o[2] = ok;
-  o[3] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3], o[4] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
+  uint32_t calc, recv;
+  const int ok = frame_crc_bits(vb, n_info, crc, &calc, &recv);
+  frame_row_write(rows + (int64_t)f.row * 5, calc, recv, ok, sh);
 }
 
 bool fec_poly_ok(int32_t g) { return g >= 0 && g < 128 && (g & 0x41) == 0x41; }
@@ -281,16 +243,10 @@ extern "C" int sy11_fec_check(int32_t n_frame, const sy11_fec_frame* frame_host,
   SY11_REQUIRE(fec_poly_ok(g0) && fec_poly_ok(g1), "fec_check: the generators 0%o, 0%o are not 7-bit with bits 6 and 0 set", g0, g1);
   SY11_REQUIRE(n_info >= 1 && n_info <= FEC_TMAX && (n_info + 7) / 8 <= stride_data, "fec_check: %d information bits are not 1 .. %d or leave the %ld bytes of a data row", n_info,
                FEC_TMAX, (long)stride_data);
-  SY11_REQUIRE(crc->width == 0 || (crc->width >= 8 && crc->width <= 32), "fec_check: a CRC of %d bits is not 0 (none) or 8 .. 32", crc->width);
-  if (crc->width) {
-    const uint64_t all = (1ull << crc->width) - 1ull;
-    SY11_REQUIRE(n_info > crc->width, "fec_check: %d information bits do not exceed the CRC's %d", n_info, crc->width);
-    SY11_REQUIRE((crc->poly & ~all) == 0 && (crc->init & ~all) == 0 && (crc->xorout & ~all) == 0 && (crc->refin | crc->refout) >> 1 == 0,
-                 "fec_check: poly / init / xorout beyond the CRC's %d bits, or refin / refout not 0 or 1", crc->width);
-    SY11_REQUIRE(!crc->refin || (n_info - crc->width) % 8 == 0, "fec_check: refin needs whole bytes before the check field, not %d bits", n_info - crc->width);
-  }
+  int rc = frame_crc_refused("fec_check", crc, n_info, false);
+  if (rc != SY11_OK) return rc;
   int32_t t_max = 0;
-  const int rc = fec_check_frames("fec_check", n_frame, frame_host, n_rows, &t_max);
+  rc = fec_check_frames("fec_check", n_frame, frame_host, n_rows, &t_max);
   if (rc != SY11_OK) return rc;
   for (int i = 0; i < n_frame; ++i) {
     const sy11_fec_frame& s = frame_host[i];

@@ -21,8 +21,10 @@
 //    after the barrier EVERY thread adds the same words, so the loop's exit is uniform over the workgroup.  The words are written again only behind the next
 //    iteration's layer barriers.
 //  * Dynamic LDS: 2 N + 8 M + 4 n_entry + 4 (mb + 1) + 16 bytes, each part rounded up to 16: 11.8 KiB for N = 1944 at rate 1/2, 160 KiB at the most (a code
-//    beyond that is refused).  Launch 3 is bandwidth-trivial: one workgroup of 256 per frame; the CRC is a serial bit loop of one thread.
+//    beyond that is refused).  Launch 3 is bandwidth-trivial: one workgroup of 256 per frame; the CRC is a serial bit loop of one thread
+//    (frame_check.h: what launch 3 shares with fec.hip and rs.hip).
 #include "common.h"
+#include "frame_check.h"
 
 #include <vector>
 
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(256) void ldpc_check_kernel(const int32_t* __restri
                                                          int64_t stride_data, uint8_t* __restrict__ data, int32_t* __restrict__ rows) {
   __shared__ uint8_t vb[LDPC_NMAX / 8];
   __shared__ int sh[2][4];
-  const int row = frame_row[blockIdx.x], t = threadIdx.x, n_data = (K + 7) / 8;
+  const int row = frame_row[blockIdx.x], t = threadIdx.x;
   const uint8_t* src = bits + (int64_t)row * stride_bits;
   const int8_t* y = soft + (int64_t)row * stride_soft;
   int n_ch = 0, n_err = 0;
@@ -158,66 +160,13 @@ __global__ __launch_bounds__(256) void ldpc_check_kernel(const int32_t* __restri
     n_ch += v != 0;
     n_err += v != 0 && (v < 0) != x;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) n_ch += __shfl_xor(n_ch, d), n_err += __shfl_xor(n_err, d);
-  if ((t & 63) == 0) sh[0][t >> 6] = n_ch, sh[1][t >> 6] = n_err;
-  // the information bits, de-whitened, packed MSB first; zeros after them
-  uint8_t* dst = data + (int64_t)row * stride_data;
-  for (int64_t b = t; b < stride_data; b += 256) {
-    int byte = 0;
-    if (b < n_data) {
-      byte = src[b];
-      for (int i = 0; i < 8; ++i) {
-        const int at = (int)b * 8 + i;
-        if (at >= K) byte &= ~(0x80 >> i);
-        else if (whiten) byte ^= (whiten[at] & 1) << (7 - i);
-      }
-      vb[b] = (uint8_t)byte;
-    }
-    dst[b] = (uint8_t)byte;
-  }
+  frame_count_reduce(n_ch, n_err, sh, t);
+  frame_dewhiten_pack(src, K, whiten, stride_data, data + (int64_t)row * stride_data, vb, t);
   __syncthreads();
   if (t != 0) return;
-  int32_t* o = rows + (int64_t)row * 5;
-  uint32_t calc = 0, recv = 0;
-  int ok = -1;
-  if (crc.width) {
-    const int W = crc.width, n_msg = K - W;
-    const uint64_t top = 1ull << (W - 1), all = (top << 1) - 1ull;
-    uint64_t reg = crc.init & all;
-    for (int k = 0; k < n_msg; ++k) {
-      const int at = crc.refin ? (k & ~7) | (7 - (k & 7)) : k;              // with refin each group of 8 bits is taken LSB first
-      const uint64_t bit = (vb[at >> 3] >> (7 - (at & 7))) & 1;
-      const uint64_t fb = ((reg >> (W - 1)) & 1ull) ^ bit;
-      reg = (reg << 1) & all;
-      if (fb) reg ^= crc.poly;
-    }
-    if (crc.refout) {
-      uint64_t r = 0;
-      for (int i = 0; i < W; ++i) r |= ((reg >> i) & 1ull) << (W - 1 - i);
-      reg = r;
-    }
-    calc = (uint32_t)((reg ^ crc.xorout) & all);
-    uint64_t got = 0;
-    for (int k = n_msg; k < K; ++k) got = (got << 1) | ((vb[k >> 3] >> (7 - (k & 7))) & 1);
-    recv = (uint32_t)got;
-    ok = calc == recv;
-  }
-  o[0] = (int32_t)calc, o[1] = (int32_t)recv, o[2] = ok;
-  o[3] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3], o[4] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-}
-
-// every frame's row inside the tables and named once
-int ldpc_check_rows(const char* what, int32_t n_frame, const int32_t* row_host, int64_t n_rows) {
-  SY11_REQUIRE(n_frame > 0 && n_rows > 0 && n_rows < (1LL << 31), "%s: need frames and rows below 2^31 (n_frame=%d n_rows=%ld)", what, n_frame, (long)n_rows);
-  std::vector<bool> seen((size_t)n_rows, false);
-  for (int i = 0; i < n_frame; ++i) {
-    const int32_t r = row_host[i];
-    SY11_REQUIRE(r >= 0 && r < n_rows, "%s: frame %d reads row %d of a table of %ld rows", what, i, r, (long)n_rows);
-    SY11_REQUIRE(!seen[(size_t)r], "%s: frame %d reads row %d, which an earlier frame of this call reads", what, i, r);
-    seen[(size_t)r] = true;
-  }
-  return SY11_OK;
+  uint32_t calc, recv;
+  const int ok = frame_crc_bits(vb, K, crc, &calc, &recv);
+  frame_row_write(rows + (int64_t)row * 5, calc, recv, ok, sh);
 }
 
 }  // namespace
@@ -263,7 +212,7 @@ extern "C" int sy11_ldpc_decode(int32_t n_frame, const int32_t* row_host, const 
   for (int j = 0; j < c.nb; ++j) SY11_REQUIRE(weight[(size_t)j] >= 1, "ldpc_decode: column %d of the code has no entry", j);
   const int64_t lds = ldpc_lds_bytes(N, M, c.n_entry, c.mb);
   SY11_REQUIRE(lds <= LDPC_LDS_MAX, "ldpc_decode: the code needs %ld bytes of LDS (2 N + 8 M + 4 entries), more than the %ld of a compute unit", (long)lds, (long)LDPC_LDS_MAX);
-  const int rc = ldpc_check_rows("ldpc_decode", n_frame, row_host, n_rows);
+  const int rc = frame_rows_once("ldpc_decode", n_frame, row_host, n_rows);
   if (rc != SY11_OK) return rc;
   SY11_REQUIRE(stride_soft >= N && stride_soft <= LDPC_NMAX, "ldpc_decode: the %d soft bits leave a row of %ld bytes (at most %d)", N, (long)stride_soft, LDPC_NMAX);
   SY11_REQUIRE(stride_bits >= (N + 7) / 8 && stride_bits <= LDPC_NMAX / 8, "ldpc_decode: the %d bits leave a row of %ld bytes (at most %d)", N, (long)stride_bits, LDPC_NMAX / 8);
@@ -289,15 +238,9 @@ extern "C" int sy11_ldpc_check(int32_t n_frame, const int32_t* row_host, const i
                    stride_data <= LDPC_NMAX / 8,
                "ldpc_check: the %d soft bits, %d bits or %d information bits leave a row of %ld / %ld / %ld bytes (at most %d / %d / %d)", N, N, K, (long)stride_soft,
                (long)stride_bits, (long)stride_data, LDPC_NMAX, LDPC_NMAX / 8, LDPC_NMAX / 8);
-  SY11_REQUIRE(crc->width == 0 || (crc->width >= 8 && crc->width <= 32), "ldpc_check: a CRC of %d bits is not 0 (none) or 8 .. 32", crc->width);
-  if (crc->width) {
-    const uint64_t all = (1ull << crc->width) - 1ull;
-    SY11_REQUIRE(K > crc->width, "ldpc_check: %d information bits do not exceed the CRC's %d", K, crc->width);
-    SY11_REQUIRE((crc->poly & ~all) == 0 && (crc->init & ~all) == 0 && (crc->xorout & ~all) == 0 && (crc->refin | crc->refout) >> 1 == 0,
-                 "ldpc_check: poly / init / xorout beyond the CRC's %d bits, or refin / refout not 0 or 1", crc->width);
-    SY11_REQUIRE(!crc->refin || (K - crc->width) % 8 == 0, "ldpc_check: refin needs whole bytes before the check field, not %d bits", K - crc->width);
-  }
-  const int rc = ldpc_check_rows("ldpc_check", n_frame, row_host, n_rows);
+  int rc = frame_crc_refused("ldpc_check", crc, K, false);
+  if (rc != SY11_OK) return rc;
+  rc = frame_rows_once("ldpc_check", n_frame, row_host, n_rows);
   if (rc != SY11_OK) return rc;
   hipLaunchKernelGGL(ldpc_check_kernel, dim3(n_frame), dim3(256), 0, (hipStream_t)stream, row, (int)N, (int)K, whiten, *crc, stride_soft, soft, stride_bits, bits, stride_data, data,
                      rows);

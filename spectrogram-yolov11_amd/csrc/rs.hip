@@ -21,9 +21,9 @@
 //  * syndromes: a lane holds 4 bytes, S_j is the wave's XOR over the lanes' terms, lane j keeps S_j.  All zero (a wave-uniform test) skips the rest.
 //    Berlekamp-Massey: nroots steps, lane i holds Lambda_i and B_i, the discrepancy is a wave XOR.  Chien: 4 of the 255 positions per lane, the
 //    roots as 4 ballot words.  Forney: lane r takes the r-th root.  Every branch around a wave-level operation is wave-uniform.
+//  * Launch 2: one wave per frame; the CRC is the byte-serial form of frame_check.h, which also holds the refusals of a CRC and of a table of rows.
 #include "common.h"
-
-#include <vector>
+#include "frame_check.h"
 
 namespace {
 
@@ -239,28 +239,8 @@ __global__ __launch_bounds__(64) void rs_check_kernel(const int32_t* __restrict_
   __syncthreads();
   if (lane != 0) return;
   int32_t* o = rows + (int64_t)row * 6;
-  uint32_t calc = 0, recv = 0;
-  int ok = -1;
-  if (crc.width) {
-    const int W = crc.width, n_msg = n_bytes - W / 8;
-    // the register kept at the top of 32 bits (W is 8, 16, 24 or 32): a byte is XORed onto its top and shifted out in 8 steps
-    const int up = 32 - W;
-    const uint32_t poly = crc.poly << up;
-    uint32_t top = crc.init << up;
-    for (int b = 0; b < n_msg; ++b) {
-      const uint32_t byte = vb[b];
-      top ^= crc.refin ? __brev(byte) : byte << 24;               // with refin a byte is taken LSB first
-#pragma unroll
-      for (int i = 0; i < 8; ++i) top = (top << 1) ^ ((top >> 31) ? poly : 0u);
-    }
-    uint32_t reg = top >> up;
-    if (crc.refout) reg = __brev(reg) >> up;
-    calc = reg ^ crc.xorout;
-    uint64_t got = 0;
-    for (int b = n_msg; b < n_bytes; ++b) got = (got << 8) | vb[b];
-    recv = (uint32_t)got;
-    ok = calc == recv;
-  }
+  uint32_t calc, recv;
+  const int ok = frame_crc_bytes(vb, n_bytes, crc, &calc, &recv);
   o[0] = n_failed, o[1] = n_err, o[2] = n_bit, o[3] = (int32_t)calc, o[4] = (int32_t)recv, o[5] = ok;
 }
 
@@ -268,7 +248,8 @@ int rs_gcd(int a, int b) { return b ? rs_gcd(b, a % b) : a; }
 
 // the checks the two launches share: the code, and every frame's row inside the tables and named once
 int rs_check_args(const char* what, int32_t n_frame, const int32_t* row_host, const sy11_rs_code* code, int64_t n_rows) {
-  SY11_REQUIRE(n_frame > 0 && n_rows > 0 && n_rows < (1LL << 31), "%s: need frames and rows below 2^31 (n_frame=%d n_rows=%ld)", what, n_frame, (long)n_rows);
+  const int rc = frame_rows_once(what, n_frame, row_host, n_rows);
+  if (rc != SY11_OK) return rc;
   const sy11_rs_code& c = *code;
   SY11_REQUIRE(c.k >= 1 && c.k < c.n && c.n <= 255 && c.n - c.k <= RS_NROOTS_MAX, "%s: the code (n=%d, k=%d) is not 1 <= k < n <= 255 with n - k <= %d", what, c.n, c.k, RS_NROOTS_MAX);
   SY11_REQUIRE(c.fcr >= 0 && c.fcr <= 254, "%s: fcr %d is not in [0, 254]", what, c.fcr);
@@ -279,13 +260,6 @@ int rs_check_args(const char* what, int32_t n_frame, const int32_t* row_host, co
   int order = 0;
   do v = rs_mul_slow(v, 2, (unsigned)c.poly), ++order; while (v != 1 && order < 256);
   SY11_REQUIRE(order == 255, "%s: the field polynomial 0x%x is not primitive (x has order %d)", what, c.poly, order);
-  std::vector<bool> seen((size_t)n_rows, false);
-  for (int i = 0; i < n_frame; ++i) {
-    const int32_t r = row_host[i];
-    SY11_REQUIRE(r >= 0 && r < n_rows, "%s: frame %d reads row %d of a table of %ld rows", what, i, r, (long)n_rows);
-    SY11_REQUIRE(!seen[(size_t)r], "%s: frame %d reads row %d, which an earlier frame of this call reads", what, i, r);
-    seen[(size_t)r] = true;
-  }
   return SY11_OK;
 }
 
@@ -318,13 +292,8 @@ extern "C" int sy11_rs_check(int32_t n_frame, const int32_t* row_host, const int
   const int n_bytes = code->interleave * code->k;
   SY11_REQUIRE(stride_info < (1LL << 31) && n_bytes <= stride_info, "rs_check: the %d x %d information bytes leave the %ld bytes of an info row", code->interleave, code->k,
                (long)stride_info);
-  SY11_REQUIRE(crc->width == 0 || (crc->width >= 8 && crc->width <= 32 && crc->width % 8 == 0), "rs_check: a CRC of %d bits is not 0 (none), 8, 16, 24 or 32", crc->width);
-  if (crc->width) {
-    const uint64_t all = (1ull << crc->width) - 1ull;
-    SY11_REQUIRE(8 * n_bytes > crc->width, "rs_check: %d information bytes do not exceed the CRC's %d bits", n_bytes, crc->width);
-    SY11_REQUIRE((crc->poly & ~all) == 0 && (crc->init & ~all) == 0 && (crc->xorout & ~all) == 0 && (crc->refin | crc->refout) >> 1 == 0,
-                 "rs_check: poly / init / xorout beyond the CRC's %d bits, or refin / refout not 0 or 1", crc->width);
-  }
+  const int bad = frame_crc_refused("rs_check", crc, 8 * (int64_t)n_bytes, true);
+  if (bad != SY11_OK) return bad;
   hipLaunchKernelGGL(rs_check_kernel, dim3(n_frame), dim3(RS_WAVE), 0, (hipStream_t)stream, row, (int)code->interleave, (int)code->k, *crc, stride_info, info, cw, rows);
   SY11_LAUNCH_CHECK("rs_check");
   return SY11_OK;

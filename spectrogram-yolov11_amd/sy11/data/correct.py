@@ -20,13 +20,12 @@ matrix applied to every byte before and after the code) is out of scope; so are 
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 
 import numpy as np
 import torch
 
+from ._frame_table import FrameTable, frame_columns, unpack_check
 from .decode import _crc_spec, _is_int
 
 # n, k, the field polynomial, the first consecutive root and the primitive element's power
@@ -175,59 +174,28 @@ def plan_correct(decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=Non
     return CorrectPlan(spec, I, offset, check, d.valid)
 
 
-class Corrected:
+class Corrected(FrameTable):
     """One row per frame of the ``Decoded``, in its order, each a numpy array over the frames: ``valid`` and ``reason`` ("undecoded": the decoder left the frame
     out), ``clip``, ``word``, ``position``, ``n_failed`` (codewords that could not be corrected), ``byte_errors`` and ``bit_errors`` (corrected, summed over the other
     codewords), ``ok`` (valid and n_failed == 0), ``crc_ok`` (bool; all True without a ``crc``), ``crc_calc`` and ``crc_recv`` (uint32); an invalid frame's row is zeros
     (``ok`` and ``crc_ok`` False).  ``errors``: (frames, interleave) int64, the byte errors corrected in every codeword, -1 for one that could not be corrected (its
     bytes pass through), 0 for an invalid frame.  ``data``: (frames, interleave k) uint8 on the DEVICE, the information bytes codeword after codeword;
     ``message(k)`` is what precedes the check field.  ``rows`` / ``cls`` / ``conf`` / ``names`` come from the frames.  ``raw`` keeps the device buffers ``cw`` and ``rows`` (None
-    when nothing was launched)."""
+    when nothing was launched).  ``save(directory)`` writes ``correct.npz`` and ``correct.json``; the table itself is ``_frame_table.FrameTable``."""
 
     COLUMNS = ("valid", "clip", "word", "position", "n_failed", "byte_errors", "bit_errors", "ok", "crc_ok", "crc_calc", "crc_recv")
+    EXTRA, STEM = ("errors",), "correct"
 
     def __init__(self, plan, cols, reason, errors, data, raw, rows=None, cls=None, conf=None, names=None):
-        self.plan, self.raw, self.data, self.reason, self.errors = plan, raw, data, reason, errors
-        self.rows, self.cls, self.conf, self.names = rows, cls, conf, names
-        for key in self.COLUMNS:
-            setattr(self, key, cols[key])
+        super().__init__(plan, cols, reason, data, raw, rows=rows, cls=cls, conf=conf, names=names)
+        self.errors = errors
 
-    def __len__(self):
-        return self.valid.shape[0]
+    def _header(self):
+        p = self.plan
+        return {"code": p.code, "interleave": p.interleave, "offset": p.offset, "crc": p.crc}
 
-    def __getitem__(self, k):
-        """Frame k as a dict of its scalars."""
-        k = range(len(self))[k]
-        d = {c: getattr(self, c)[k].item() for c in self.COLUMNS}
-        d.update(reason=str(self.reason[k]), errors=self.errors[k].tolist())
-        return d
-
-    def message(self, k):
-        """The information bytes of frame ``k`` before the check field, ``bytes``."""
-        k = range(len(self))[k]
-        b = self.data[k].cpu().numpy()
-        return b[:b.shape[0] - (self.plan.crc["width"] // 8 if self.plan.crc else 0)].tobytes()
-
-    def save(self, directory):
-        """Write ``correct.npz`` (every column, the reasons, the codewords' errors and the information bytes) and ``correct.json`` (the arguments and one record per
-        frame, its message as hex).  -> the directory."""
-        directory = os.fspath(directory)
-        os.makedirs(directory, exist_ok=True)
-        arrays = {key: getattr(self, key) for key in self.COLUMNS}
-        arrays.update(data=self.data.cpu().numpy(), errors=self.errors, reason=np.asarray([str(r) for r in self.reason], dtype=str))
-        np.savez(os.path.join(directory, "correct.npz"), **arrays)
-        p, out = self.plan, []
-        tail = p.crc["width"] // 8 if p.crc else 0
-        for k in range(len(self)):
-            rec = {c: getattr(self, c)[k].item() for c in self.COLUMNS}
-            cls = None if self.cls is None else int(self.cls[int(self.clip[k])])
-            rec.update(reason=str(self.reason[k]), errors=self.errors[k].tolist(), message=arrays["data"][k, :p.n_bytes - tail].tobytes().hex() if self.valid[k] else None,
-                       name=None if cls is None or not self.names else self.names.get(cls))
-            rec["class"] = cls
-            out.append(rec)
-        with open(os.path.join(directory, "correct.json"), "w") as f:
-            json.dump({"code": p.code, "interleave": p.interleave, "offset": p.offset, "crc": p.crc, "file": "correct.npz", "frames": out}, f, indent=1)
-        return directory
+    def _message(self, row):
+        return row[:self.plan.n_bytes - (self.plan.crc["width"] // 8 if self.plan.crc else 0)].tobytes()
 
 
 def correct_decoded(decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=None):
@@ -242,10 +210,7 @@ def correct_decoded(decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=
     n, I = len(plan), plan.interleave
     meta = dict(rows=d.rows, cls=d.cls, conf=d.conf, names=d.names)
     dev = d.data.device
-    cols = {"valid": plan.valid.copy(), "clip": np.asarray(d.clip, dtype=np.int64).copy(), "word": np.asarray(d.word, dtype=np.int64).copy(),
-            "position": np.asarray(d.position, dtype=np.int64).copy(), "n_failed": np.zeros(n, dtype=np.int64), "byte_errors": np.zeros(n, dtype=np.int64),
-            "bit_errors": np.zeros(n, dtype=np.int64), "ok": np.zeros(n, dtype=bool), "crc_ok": np.zeros(n, dtype=bool), "crc_calc": np.zeros(n, dtype=np.uint32),
-            "crc_recv": np.zeros(n, dtype=np.uint32)}
+    cols = frame_columns(plan.valid, d, ("n_failed", "byte_errors", "bit_errors"), bools=("ok",))
     errors = np.zeros((n, I), dtype=np.int64)
     raw = {"cw": None, "rows": None}
     at = np.flatnonzero(plan.valid)
@@ -261,8 +226,7 @@ def correct_decoded(decoded, *, code="dvb-204-188", interleave=1, offset=0, crc=
     h = torch.cat((rows, cw.reshape(n, 2 * I)), 1).cpu().numpy()             # one copy: the six of launch 2, then (errors, bit_errors) per codeword
     v = plan.valid
     cols["n_failed"][v], cols["byte_errors"][v], cols["bit_errors"][v] = h[v, 0], h[v, 1], h[v, 2]
-    cols["crc_calc"][v], cols["crc_recv"][v] = h[v, 3].astype(np.int32).view(np.uint32), h[v, 4].astype(np.int32).view(np.uint32)
-    cols["crc_ok"][v] = h[v, 5] != 0                                        # -1 without a crc: True
+    unpack_check(cols, v, h, 3)
     cols["ok"] = v & (cols["n_failed"] == 0)
     errors[v] = h[v, 6::2]
     return Corrected(plan, cols, plan.reason, errors, info, raw, **meta)

@@ -17,12 +17,12 @@ symbol; its received stream starts at symbol ``sym_off[i] + p + L`` of the demod
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 
 import numpy as np
 import torch
+
+from ._frame_table import BitTable, frame_columns, unpack_check
 
 # laid out as sy11_fec_frame (include/sy11.h)
 FECFRAME = np.dtype([("sym_off", "<i8"), ("T", "<i4"), ("order", "<i4"), ("q", "<i4"), ("tail", "<i4"), ("row", "<i4"), ("scale", "<f4")])
@@ -146,16 +146,44 @@ class DecodePlan:
         return fr, at
 
 
-def plan_decode(frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
-    """The ``DecodePlan`` of ``frames`` (a ``Frames``) on ``demodulation`` (the ``Demodulation`` it was found in).  Every argument error is a ``ValueError`` raised
-    here, before anything touches the device; a frame that cannot be decoded is an entry with ``valid`` False and a ``reason``."""
-    what = "plan_decode"
+def _plan_frames(what, frames, demodulation, n_info, whiten, crc, soft_scale, make):
+    """What the plan of a decoder checks and derives whatever its code: ``frames`` and ``demodulation`` belong together; ``whiten`` (cut to the ``n_info`` information bits),
+    ``crc`` and ``soft_scale``; every frame's order, gain, first payload symbol and payload symbols, from which ``make(whiten, crc, soft_scale, order, gain, sym_off,
+    n_payload)`` builds the plan; a payload that no frame's code fits is refused.  -> the plan."""
     f, d = frames, demodulation
     if not all(hasattr(f, k) for k in ("plan", "clip", "word", "position", "rotation", "n_payload")) or not all(hasattr(d, k) for k in ("gain", "n_symbols", "order")):
         raise ValueError(f"{what}: give the Frames of find_frames and the Demodulation they were found in")
     fp = f.plan
-    if np.asarray(d.n_symbols).shape != fp.n_symbols.shape or np.asarray(d.gain).shape != fp.n_symbols.shape or not np.array_equal(np.asarray(d.n_symbols, dtype=np.int64), fp.n_symbols) or not np.array_equal(np.asarray(d.order, dtype=np.int64), fp.order):
+    if np.asarray(d.n_symbols).shape != fp.n_symbols.shape or np.asarray(d.gain).shape != fp.n_symbols.shape \
+            or not np.array_equal(np.asarray(d.n_symbols, dtype=np.int64), fp.n_symbols) or not np.array_equal(np.asarray(d.order, dtype=np.int64), fp.order):
         raise ValueError(f"{what}: the frames were not found in this demodulation (the clips' count, n_symbols or order differ)")
+    if whiten is not None:
+        whiten = _bit_array(what, "whiten", whiten)
+        if whiten.shape[0] < n_info:
+            raise ValueError(f"{what}: `whiten` holds {whiten.shape[0]} bits, fewer than n_info = {n_info}")
+        whiten = whiten[:n_info].copy()
+    spec = _crc_spec(what, crc, n_info)
+    if isinstance(soft_scale, (bool, np.bool_)) or not isinstance(soft_scale, (int, float, np.integer, np.floating)) or not math.isfinite(float(soft_scale)) \
+            or not 0.0 < float(soft_scale) <= 127.0:
+        raise ValueError(f"{what}: soft_scale must be finite and in (0, 127], got {soft_scale!r}")
+    clip, word = np.asarray(f.clip, dtype=np.int64), np.asarray(f.word, dtype=np.int64)
+    order = fp.order[clip]
+    gain = np.asarray(d.gain, dtype=np.float64)[clip]
+    sym_off = fp.sym_off[clip] + np.asarray(f.position, dtype=np.int64) + fp.L[clip, word]
+    plan = make(whiten, spec, float(soft_scale), order, gain, sym_off, np.asarray(f.n_payload, dtype=np.int64))
+    n_least = -(-plan.n_coded // 2)
+    if fp.payload < n_least:
+        raise ValueError(f"{what}: the frames were read with payload = {fp.payload} symbols, but the code needs {n_least} at order 4 ({plan.n_coded} at order 2): "
+                         f"no frame could be decoded")
+    if order.size and fp.payload < int(plan.n_need.min()):
+        raise ValueError(f"{what}: the frames were read with payload = {fp.payload} symbols, but the code needs {int(plan.n_need.min())}: no frame could be decoded")
+    return plan
+
+
+def plan_decode(frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
+    """The ``DecodePlan`` of ``frames`` (a ``Frames``) on ``demodulation`` (the ``Demodulation`` it was found in).  Every argument error is a ``ValueError`` raised
+    here, before anything touches the device; a frame that cannot be decoded is an entry with ``valid`` False and a ``reason``."""
+    what = "plan_decode"
     if not isinstance(tail, (bool, np.bool_)):
         raise ValueError(f"{what}: tail must be a bool, got {tail!r}")
     tail = bool(tail)
@@ -176,99 +204,26 @@ def plan_decode(frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=
         pattern = _bit_array(what, "puncture", puncture)
         if pattern.shape[0] % 2 or pattern.shape[0] > 64 or not pattern.any():
             raise ValueError(f"{what}: the puncture pattern's period must be even and at most 64, and it must hold a 1; got {pattern.tolist()}")
-    if whiten is not None:
-        whiten = _bit_array(what, "whiten", whiten)
-        if whiten.shape[0] < n_info:
-            raise ValueError(f"{what}: `whiten` holds {whiten.shape[0]} bits, fewer than n_info = {n_info}")
-        whiten = whiten[:n_info].copy()
-    spec = _crc_spec(what, crc, n_info)
-    if isinstance(soft_scale, (bool, np.bool_)) or not isinstance(soft_scale, (int, float, np.integer, np.floating)) or not math.isfinite(float(soft_scale)) \
-            or not 0.0 < float(soft_scale) <= 127.0:
-        raise ValueError(f"{what}: soft_scale must be finite and in (0, 127], got {soft_scale!r}")
-    clip, word = np.asarray(f.clip, dtype=np.int64), np.asarray(f.word, dtype=np.int64)
-    order = fp.order[clip]
-    L = fp.L[clip, word]
-    gain = np.asarray(d.gain, dtype=np.float64)[clip]
-    sym_off = fp.sym_off[clip] + np.asarray(f.position, dtype=np.int64) + L
-    plan = DecodePlan(n_info, polys, tail, T, pattern, whiten, spec, float(soft_scale), order, gain, sym_off, np.asarray(f.n_payload, dtype=np.int64))
-    n_least = -(-plan.n_coded // 2)
-    if fp.payload < n_least:
-        raise ValueError(f"{what}: the frames were read with payload = {fp.payload} symbols, but the code needs {n_least} at order 4 ({plan.n_coded} at order 2): "
-                         f"no frame could be decoded")
-    if order.size and fp.payload < int(plan.n_need.min()):
-        raise ValueError(f"{what}: the frames were read with payload = {fp.payload} symbols, but the code needs {int(plan.n_need.min())}: no frame could be decoded")
-    return plan
+    return _plan_frames(what, frames, demodulation, n_info, whiten, crc, soft_scale, lambda *per_frame: DecodePlan(n_info, polys, tail, T, pattern, *per_frame))
 
 
-class Decoded:
+class Decoded(BitTable):
     """One row per frame of the ``Frames``, in its order, each a numpy array over the frames: ``valid`` and ``reason`` ("short": fewer payload symbols than the
     code needs; "gain": the clip's gain is not a positive number), ``clip``, ``word``, ``position``, ``metric`` (the final path metric), ``end_state``,
     ``channel_errors`` and ``n_channel`` (received bits that differ from the re-encoded decision, of those that are not erasures), ``ber`` (their ratio, NaN at
     0), ``crc_ok`` (bool; all True without a ``crc``), ``crc_calc`` and ``crc_recv`` (uint32); an invalid frame's row is zeros (``ber`` NaN, ``crc_ok`` False).
     ``data``: (frames, bytes) uint8 on the DEVICE, the de-whitened information bits packed MSB first; ``bits(k)`` unpacks a row on the host, ``message(k)`` is
     what precedes the check field; ``soft(k)`` the frame's 2T soft bits, a device view.  ``rows`` / ``cls`` / ``conf`` / ``names`` come from the frames.  ``raw`` keeps the
-    device buffers ``soft``, ``decided`` (the packed decisions of launch 2), ``out`` and ``rows`` (None when nothing was launched)."""
+    device buffers ``soft``, ``decided`` (the packed decisions of launch 2), ``out`` and ``rows`` (None when nothing was launched).  ``save(directory)`` writes ``decode.npz``
+    and ``decode.json``; the table itself is ``_frame_table.BitTable``."""
 
     COLUMNS = ("valid", "clip", "word", "position", "metric", "end_state", "channel_errors", "n_channel", "ber", "crc_ok", "crc_calc", "crc_recv")
+    STEM = "decode"
 
-    def __init__(self, plan, cols, reason, data, raw, rows=None, cls=None, conf=None, names=None):
-        self.plan, self.raw, self.data, self.reason = plan, raw, data, reason
-        self.rows, self.cls, self.conf, self.names = rows, cls, conf, names
-        for k in self.COLUMNS:
-            setattr(self, k, cols[k])
-
-    def __len__(self):
-        return self.valid.shape[0]
-
-    def __getitem__(self, k):
-        """Frame k as a dict of its scalars."""
-        k = range(len(self))[k]
-        d = {c: getattr(self, c)[k].item() for c in self.COLUMNS}
-        d["reason"] = str(self.reason[k])
-        return d
-
-    def bits(self, k):
-        """The ``n_info`` de-whitened information bits of frame ``k`` on the host, uint8, the first bit first."""
-        k = range(len(self))[k]
-        return np.unpackbits(self.data[k].cpu().numpy())[:self.plan.n_info].astype(np.uint8)
-
-    def message(self, k):
-        """The bits of frame ``k`` before the check field: ``bytes`` when they are a multiple of 8 (MSB first), the uint8 bit array otherwise."""
-        b = self.bits(k)
-        b = b[:b.shape[0] - (self.plan.crc["width"] if self.plan.crc else 0)]
-        return np.packbits(b).tobytes() if b.shape[0] % 8 == 0 else b
-
-    def soft(self, k):
-        """The ``2T`` soft bits of frame ``k``, int8, a view of the device buffer (zeros for an invalid frame)."""
-        k = range(len(self))[k]
-        if self.raw["soft"] is None:
-            return torch.zeros(2 * self.plan.T, dtype=torch.int8, device=self.data.device)
-        return self.raw["soft"][k, :2 * self.plan.T]
-
-    def save(self, directory):
-        """Write ``decode.npz`` (every column, the reasons and the packed data) and ``decode.json`` (the arguments and one record per frame, its message as
-        hex where it is whole bytes).  -> the directory."""
-        directory = os.fspath(directory)
-        os.makedirs(directory, exist_ok=True)
-        arrays = {k: getattr(self, k) for k in self.COLUMNS}
-        arrays.update(data=self.data.cpu().numpy(), reason=np.asarray([str(r) for r in self.reason], dtype=str))
-        np.savez(os.path.join(directory, "decode.npz"), **arrays)
-        p, out = self.plan, []
-        data = arrays["data"]
-        for k in range(len(self)):
-            rec = {c: getattr(self, c)[k].item() for c in self.COLUMNS}
-            rec["ber"] = rec["ber"] if math.isfinite(rec["ber"]) else None
-            b = np.unpackbits(data[k])[:p.n_info]
-            b = b[:b.shape[0] - (p.crc["width"] if p.crc else 0)]
-            cls = None if self.cls is None else int(self.cls[int(self.clip[k])])
-            rec.update(reason=str(self.reason[k]), message=np.packbits(b).tobytes().hex() if self.valid[k] and b.shape[0] % 8 == 0 else None,
-                       name=None if cls is None or not self.names else self.names.get(cls))
-            rec["class"] = cls
-            out.append(rec)
-        with open(os.path.join(directory, "decode.json"), "w") as f:
-            json.dump({"n_info": p.n_info, "polys": list(p.polys), "tail": p.tail, "puncture": None if p.pattern is None else p.pattern.tolist(),
-                       "whiten": None if p.whiten is None else p.whiten.tolist(), "crc": p.crc, "soft_scale": p.soft_scale, "file": "decode.npz", "frames": out}, f, indent=1)
-        return directory
+    def _header(self):
+        p = self.plan
+        return {"n_info": p.n_info, "polys": list(p.polys), "tail": p.tail, "puncture": None if p.pattern is None else p.pattern.tolist(),
+                "whiten": None if p.whiten is None else p.whiten.tolist(), "crc": p.crc, "soft_scale": p.soft_scale}
 
 
 def decode_frames(frames, demodulation, *, n_info, polys=(0o171, 0o133), puncture=None, tail=True, whiten=None, crc=None, soft_scale=32.0):
@@ -277,7 +232,7 @@ def decode_frames(frames, demodulation, *, n_info, polys=(0o171, 0o133), punctur
     pattern over the mother stream, 1 = sent; ``tail``: six zero bits end the frame; ``whiten``: the 0/1 sequence XORed onto the information bits
     (``lfsr_bits``); ``crc``: a name of ``CRCS`` or a Rocksoft dict; ``soft_scale``: the soft value of a clean component.  ``frames`` must have been read with
     ``payload`` of at least ``n_need`` symbols.  Without a valid frame nothing is launched."""
-    from .. import _lib, ops
+    from .. import ops
     from .frames import _packed_symbols
     f, d = frames, demodulation
     plan = plan_decode(f, d, n_info=n_info, polys=polys, puncture=puncture, tail=tail, whiten=whiten, crc=crc, soft_scale=soft_scale)
@@ -285,10 +240,7 @@ def decode_frames(frames, demodulation, *, n_info, polys=(0o171, 0o133), punctur
     meta = dict(rows=f.rows, cls=f.cls, conf=f.conf, names=f.names)
     dev = f.payload.device
     n_data = (plan.n_info + 7) // 8
-    cols = {"valid": plan.valid.copy(), "clip": np.asarray(f.clip, dtype=np.int64).copy(), "word": np.asarray(f.word, dtype=np.int64).copy(),
-            "position": np.asarray(f.position, dtype=np.int64).copy(), "metric": np.zeros(n, dtype=np.int64), "end_state": np.zeros(n, dtype=np.int64),
-            "channel_errors": np.zeros(n, dtype=np.int64), "n_channel": np.zeros(n, dtype=np.int64), "ber": np.full(n, np.nan), "crc_ok": np.zeros(n, dtype=bool),
-            "crc_calc": np.zeros(n, dtype=np.uint32), "crc_recv": np.zeros(n, dtype=np.uint32)}
+    cols = frame_columns(plan.valid, f, ("metric", "end_state"), channel=True)
     raw = {"soft": None, "decided": None, "out": None, "rows": None}
     fr, at = plan.table(np.asarray(f.rotation, dtype=np.int64), f.plan.order[cols["clip"]])
     if at.shape[0] == 0:
@@ -307,9 +259,5 @@ def decode_frames(frames, demodulation, *, n_info, polys=(0o171, 0o133), punctur
     h = torch.cat((out, rows), 1).cpu().numpy()                             # one copy: metric, end state, crc_calc, crc_recv, crc_ok, errors, n_channel
     v = plan.valid
     cols["metric"][v], cols["end_state"][v] = h[v, 0], h[v, 1]
-    cols["crc_calc"][v], cols["crc_recv"][v] = h[v, 2].astype(np.int32).view(np.uint32), h[v, 3].astype(np.int32).view(np.uint32)
-    cols["crc_ok"][v] = h[v, 4] != 0                                        # -1 without a crc: True
-    cols["channel_errors"][v], cols["n_channel"][v] = h[v, 5], h[v, 6]
-    some = v & (cols["n_channel"] > 0)
-    cols["ber"][some] = cols["channel_errors"][some] / cols["n_channel"][some]
+    unpack_check(cols, v, h, 2, channel=True)
     return Decoded(plan, cols, plan.reason, data, raw, **meta)

@@ -21,14 +21,11 @@ codes, offset min-sum and sum-product, an outer BCH code, soft output to a later
 """
 from __future__ import annotations
 
-import json
-import math
-import os
-
 import numpy as np
 import torch
 
-from .decode import DecodePlan, _bit_array, _crc_spec, _is_int
+from ._frame_table import BitTable, frame_columns, unpack_check
+from .decode import DecodePlan, _is_int, _plan_frames
 
 # laid out as sy11_ldpc_entry (include/sy11.h)
 LDPCENTRY = np.dtype([("column", "<i4"), ("shift", "<i4")])
@@ -222,42 +219,15 @@ def plan_ldpc(frames, demodulation, *, code, iterations=20, scale=12, whiten=Non
     """The ``LdpcPlan`` of ``frames`` (a ``Frames``) on ``demodulation`` (the ``Demodulation`` it was found in).  Every argument error is a ``ValueError`` raised here,
     before anything touches the device; a frame that cannot be decoded is an entry with ``valid`` False and a ``reason``."""
     what = "plan_ldpc"
-    f, d = frames, demodulation
-    if not all(hasattr(f, k) for k in ("plan", "clip", "word", "position", "rotation", "n_payload")) or not all(hasattr(d, k) for k in ("gain", "n_symbols", "order")):
-        raise ValueError(f"{what}: give the Frames of find_frames and the Demodulation they were found in")
-    fp = f.plan
-    if np.asarray(d.n_symbols).shape != fp.n_symbols.shape or np.asarray(d.gain).shape != fp.n_symbols.shape or not np.array_equal(np.asarray(d.n_symbols, dtype=np.int64), fp.n_symbols) or not np.array_equal(np.asarray(d.order, dtype=np.int64), fp.order):
-        raise ValueError(f"{what}: the frames were not found in this demodulation (the clips' count, n_symbols or order differ)")
     cd = _code_of(what, code)
     if not _is_int(iterations) or not 1 <= iterations <= ITER_MAX:
         raise ValueError(f"{what}: iterations must be an integer in [1, {ITER_MAX}], got {iterations!r}")
     if not _is_int(scale) or not 1 <= scale <= SCALE_MAX:
         raise ValueError(f"{what}: scale must be an integer in [1, {SCALE_MAX}] (sixteenths), got {scale!r}")
-    if whiten is not None:
-        whiten = _bit_array(what, "whiten", whiten)
-        if whiten.shape[0] < cd.K:
-            raise ValueError(f"{what}: `whiten` holds {whiten.shape[0]} bits, fewer than the code's K = {cd.K}")
-        whiten = whiten[:cd.K].copy()
-    spec = _crc_spec(what, crc, cd.K)
-    if isinstance(soft_scale, (bool, np.bool_)) or not isinstance(soft_scale, (int, float, np.integer, np.floating)) or not math.isfinite(float(soft_scale)) \
-            or not 0.0 < float(soft_scale) <= 127.0:
-        raise ValueError(f"{what}: soft_scale must be finite and in (0, 127], got {soft_scale!r}")
-    clip, word = np.asarray(f.clip, dtype=np.int64), np.asarray(f.word, dtype=np.int64)
-    order = fp.order[clip]
-    L = fp.L[clip, word]
-    gain = np.asarray(d.gain, dtype=np.float64)[clip]
-    sym_off = fp.sym_off[clip] + np.asarray(f.position, dtype=np.int64) + L
-    plan = LdpcPlan(cd, int(iterations), int(scale), whiten, spec, float(soft_scale), order, gain, sym_off, np.asarray(f.n_payload, dtype=np.int64))
-    n_least = -(-cd.N // 2)
-    if fp.payload < n_least:
-        raise ValueError(f"{what}: the frames were read with payload = {fp.payload} symbols, but the code needs {n_least} at order 4 ({cd.N} at order 2): no frame could be "
-                         f"decoded")
-    if order.size and fp.payload < int(plan.n_need.min()):
-        raise ValueError(f"{what}: the frames were read with payload = {fp.payload} symbols, but the code needs {int(plan.n_need.min())}: no frame could be decoded")
-    return plan
+    return _plan_frames(what, frames, demodulation, cd.K, whiten, crc, soft_scale, lambda *per_frame: LdpcPlan(cd, int(iterations), int(scale), *per_frame))
 
 
-class LdpcDecoded:
+class LdpcDecoded(BitTable):
     """One row per frame of the ``Frames``, in its order, each a numpy array over the frames: ``valid`` and ``reason`` ("short": fewer payload symbols than the code
     needs; "gain": the clip's gain is not a positive number), ``clip``, ``word``, ``position``, ``iterations`` (run), ``unsatisfied`` (checks the decision leaves open),
     ``converged`` (valid and none open), ``channel_errors`` and ``n_channel`` (received bits that differ from the decision, of those that are not erasures), ``ber`` (their
@@ -265,43 +235,16 @@ class LdpcDecoded:
     ``converged`` False).  ``data``: (frames, ceil(K / 8)) uint8 on the DEVICE, the de-whitened information bits packed MSB first; ``bits(k)`` unpacks a row on the host,
     ``message(k)`` is what precedes the check field; ``soft(k)`` the frame's N soft bits and ``posterior(k)`` its N final Q (int16), device views.  ``rows`` / ``cls`` /
     ``conf`` / ``names`` come from the frames.  ``raw`` keeps the device buffers ``soft``, ``decided`` (the packed decisions of launch 2), ``out``, ``post`` and ``rows`` (None when
-    nothing was launched).  It carries what ``plan_correct`` reads of a ``Decoded``, so ``correct`` takes it as it is."""
+    nothing was launched).  It carries what ``plan_correct`` reads of a ``Decoded``, so ``correct`` takes it as it is.  ``save(directory)`` writes ``ldpc.npz`` and ``ldpc.json``;
+    the table itself is ``_frame_table.BitTable``."""
 
     COLUMNS = ("valid", "clip", "word", "position", "iterations", "unsatisfied", "converged", "channel_errors", "n_channel", "ber", "crc_ok", "crc_calc", "crc_recv")
+    STEM = "ldpc"
 
-    def __init__(self, plan, cols, reason, data, raw, rows=None, cls=None, conf=None, names=None):
-        self.plan, self.raw, self.data, self.reason = plan, raw, data, reason
-        self.rows, self.cls, self.conf, self.names = rows, cls, conf, names
-        for k in self.COLUMNS:
-            setattr(self, k, cols[k])
-
-    def __len__(self):
-        return self.valid.shape[0]
-
-    def __getitem__(self, k):
-        """Frame k as a dict of its scalars."""
-        k = range(len(self))[k]
-        d = {c: getattr(self, c)[k].item() for c in self.COLUMNS}
-        d["reason"] = str(self.reason[k])
-        return d
-
-    def bits(self, k):
-        """The K de-whitened information bits of frame ``k`` on the host, uint8, the first bit first."""
-        k = range(len(self))[k]
-        return np.unpackbits(self.data[k].cpu().numpy())[:self.plan.n_info].astype(np.uint8)
-
-    def message(self, k):
-        """The bits of frame ``k`` before the check field: ``bytes`` when they are a multiple of 8 (MSB first), the uint8 bit array otherwise."""
-        b = self.bits(k)
-        b = b[:b.shape[0] - (self.plan.crc["width"] if self.plan.crc else 0)]
-        return np.packbits(b).tobytes() if b.shape[0] % 8 == 0 else b
-
-    def soft(self, k):
-        """The N soft bits of frame ``k``, int8, a view of the device buffer (zeros for an invalid frame)."""
-        k = range(len(self))[k]
-        if self.raw["soft"] is None:
-            return torch.zeros(self.plan.N, dtype=torch.int8, device=self.data.device)
-        return self.raw["soft"][k, :self.plan.N]
+    def _header(self):
+        p = self.plan
+        return {"code": p.code.spec(), "N": p.N, "K": p.n_info, "iterations": p.iterations, "scale": p.scale16, "whiten": None if p.whiten is None else p.whiten.tolist(),
+                "crc": p.crc, "soft_scale": p.soft_scale}
 
     def posterior(self, k):
         """The N final values Q of frame ``k``, int16 (negative = bit 1), a view of the device buffer (zeros for an invalid frame)."""
@@ -309,31 +252,6 @@ class LdpcDecoded:
         if self.raw["post"] is None:
             return torch.zeros(self.plan.N, dtype=torch.int16, device=self.data.device)
         return self.raw["post"][k, :self.plan.N]
-
-    def save(self, directory):
-        """Write ``ldpc.npz`` (every column, the reasons and the packed data) and ``ldpc.json`` (the arguments and one record per frame, its message as hex where it
-        is whole bytes).  -> the directory."""
-        directory = os.fspath(directory)
-        os.makedirs(directory, exist_ok=True)
-        arrays = {k: getattr(self, k) for k in self.COLUMNS}
-        arrays.update(data=self.data.cpu().numpy(), reason=np.asarray([str(r) for r in self.reason], dtype=str))
-        np.savez(os.path.join(directory, "ldpc.npz"), **arrays)
-        p, out = self.plan, []
-        data = arrays["data"]
-        for k in range(len(self)):
-            rec = {c: getattr(self, c)[k].item() for c in self.COLUMNS}
-            rec["ber"] = rec["ber"] if math.isfinite(rec["ber"]) else None
-            b = np.unpackbits(data[k])[:p.n_info]
-            b = b[:b.shape[0] - (p.crc["width"] if p.crc else 0)]
-            cls = None if self.cls is None else int(self.cls[int(self.clip[k])])
-            rec.update(reason=str(self.reason[k]), message=np.packbits(b).tobytes().hex() if self.valid[k] and b.shape[0] % 8 == 0 else None,
-                       name=None if cls is None or not self.names else self.names.get(cls))
-            rec["class"] = cls
-            out.append(rec)
-        with open(os.path.join(directory, "ldpc.json"), "w") as f:
-            json.dump({"code": p.code.spec(), "N": p.N, "K": p.n_info, "iterations": p.iterations, "scale": p.scale16, "whiten": None if p.whiten is None else p.whiten.tolist(),
-                       "crc": p.crc, "soft_scale": p.soft_scale, "file": "ldpc.npz", "frames": out}, f, indent=1)
-        return directory
 
 
 def decode_ldpc_frames(frames, demodulation, *, code, iterations=20, scale=12, whiten=None, crc=None, soft_scale=16.0):
@@ -351,10 +269,7 @@ def decode_ldpc_frames(frames, demodulation, *, code, iterations=20, scale=12, w
     meta = dict(rows=f.rows, cls=f.cls, conf=f.conf, names=f.names)
     dev = f.payload.device
     n_data = (K + 7) // 8
-    cols = {"valid": plan.valid.copy(), "clip": np.asarray(f.clip, dtype=np.int64).copy(), "word": np.asarray(f.word, dtype=np.int64).copy(),
-            "position": np.asarray(f.position, dtype=np.int64).copy(), "iterations": np.zeros(n, dtype=np.int64), "unsatisfied": np.zeros(n, dtype=np.int64),
-            "converged": np.zeros(n, dtype=bool), "channel_errors": np.zeros(n, dtype=np.int64), "n_channel": np.zeros(n, dtype=np.int64), "ber": np.full(n, np.nan),
-            "crc_ok": np.zeros(n, dtype=bool), "crc_calc": np.zeros(n, dtype=np.uint32), "crc_recv": np.zeros(n, dtype=np.uint32)}
+    cols = frame_columns(plan.valid, f, ("iterations", "unsatisfied"), bools=("converged",), channel=True)
     raw = {"soft": None, "decided": None, "out": None, "post": None, "rows": None}
     fr, at = plan.table(np.asarray(f.rotation, dtype=np.int64), f.plan.order[cols["clip"]])
     if at.shape[0] == 0:
@@ -375,9 +290,5 @@ def decode_ldpc_frames(frames, demodulation, *, code, iterations=20, scale=12, w
     v = plan.valid
     cols["iterations"][v], cols["unsatisfied"][v] = h[v, 0], h[v, 1]
     cols["converged"] = v & (cols["unsatisfied"] == 0)
-    cols["crc_calc"][v], cols["crc_recv"][v] = h[v, 2].astype(np.int32).view(np.uint32), h[v, 3].astype(np.int32).view(np.uint32)
-    cols["crc_ok"][v] = h[v, 4] != 0                                        # -1 without a crc: True
-    cols["channel_errors"][v], cols["n_channel"][v] = h[v, 5], h[v, 6]
-    some = v & (cols["n_channel"] > 0)
-    cols["ber"][some] = cols["channel_errors"][some] / cols["n_channel"][some]
+    unpack_check(cols, v, h, 2, channel=True)
     return LdpcDecoded(plan, cols, plan.reason, data, raw, **meta)

@@ -1072,10 +1072,10 @@ def demod_decide(sym, items, theta, r, d, rows):
     return r, d, rows
 
 
-def _u8_vector(what, name, v, dev, n=None):
+def _u8_vector(what, name, v, dev, n=None, exc=_lib.Sy11Error):
     if v.dtype != torch.uint8 or v.dim() != 1 or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or not v.is_contiguous() or v.device != dev \
             or (n is not None and v.shape[0] != n):
-        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty 1-D contiguous uint8 tensor on the symbols' device" + ("" if n is None else f" of {n} entries"))
+        raise exc(f"{what}: `{name}` must be a non-empty 1-D contiguous uint8 tensor on the symbols' device" + ("" if n is None else f" of {n} entries"))
 
 
 def _sync_items(what, items, n_sym, n_word, n_pos):
@@ -1457,6 +1457,39 @@ def _fec_fit(what, fr, stride_soft, stride_bits=None):
         raise _lib.Sy11Error(f"{what}: frame {k}: {int(fr['T'][k])} steps leave a row of {stride_soft} soft bytes" + ("" if stride_bits is None else f" or {stride_bits} bit bytes"))
 
 
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _crc_arg(what, crc, n_bits, whole_bytes, exc):
+    """The ``crc`` of a check launch over ``n_bits`` information bits: None, or a dict width / poly / init / refin / refout / xorout of 8 .. 32 bits (``whole_bytes``, the
+    byte-serial check: 8, 16, 24 or 32) -> the ``FecCrc``, checked as the library checks it (csrc/frame_check.h).  A refusal raises ``exc``."""
+    if crc is None:
+        return _lib.FecCrc()
+    try:
+        W, poly, init, xorout, refin, refout = (int(crc[k]) for k in ("width", "poly", "init", "xorout", "refin", "refout"))
+    except (KeyError, TypeError, ValueError):
+        raise exc(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
+    if W not in ((8, 16, 24, 32) if whole_bytes else range(8, 33)) or n_bits <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) \
+            or refout not in (0, 1) or (refin and (n_bits - W) % 8):
+        raise exc(f"{what}: the crc {crc!r} is not of {'8, 16, 24 or 32' if whole_bytes else '8 .. 32'} bits below the {n_bits} information bits, with fields of that width "
+                  f"(and whole bytes with refin)")
+    return _lib.FecCrc(W, poly, init, xorout, refin, refout)
+
+
+def _frame_rows(what, frames, n_rows):
+    """The rows the frames of a launch read, each inside the tables of ``n_rows`` rows and named once -> the contiguous int32 table."""
+    fr = np.asarray(frames)
+    if fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31 or not np.issubdtype(fr.dtype, np.integer):
+        raise ValueError(f"{what}: `frames` must be a non-empty 1-D integer array of the rows the frames read")
+    row = fr.astype(np.int64)
+    bad = (row < 0) | (row >= n_rows)
+    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
+        i = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
+        raise ValueError(f"{what}: frame {i} reads row {int(row[i])} of a table of {n_rows} rows (a row takes one frame)")
+    return np.ascontiguousarray(row.astype(np.int32))
+
+
 def fec_soft(sym, frames, soft, period=2, pattern=3):
     """Launch 1 of the frame decoder (sy11_fec_soft): every frame of ``frames`` — ``sy11.data.decode.FECFRAME`` records (sym_off, T, order, q, tail, row, scale):
     the payload symbols from ``sym[sym_off]`` on, turned back by ``q`` steps of 2 pi / order — writes its ``2T`` depunctured soft bits
@@ -1530,21 +1563,12 @@ def fec_check(soft, bits, frames, polys, n_info, data, rows, whiten=None, crc=No
     _fec_table(what, "data", data, torch.uint8, dev, n_rows=n, lo=1, hi=T_MAX // 8)
     _fec_table(what, "rows", rows, torch.int32, dev, n_rows=n, width=5)
     g0, g1 = _fec_polys(what, polys)
-    if isinstance(n_info, bool) or not isinstance(n_info, (int, np.integer)) or not 1 <= n_info <= T_MAX or (n_info + 7) // 8 > data.shape[1]:
+    if not _is_int(n_info) or not 1 <= n_info <= T_MAX or (n_info + 7) // 8 > data.shape[1]:
         raise _lib.Sy11Error(f"{what}: {n_info!r} information bits are not 1 .. {T_MAX} or leave the {data.shape[1]} bytes of a data row")
     n_info = int(n_info)
     if whiten is not None:
         _u8_vector(what, "whiten", whiten, dev, n_info)
-    spec = _lib.FecCrc()
-    if crc is not None:
-        try:
-            W, poly, init, xorout, refin, refout = (int(crc[k]) for k in ("width", "poly", "init", "xorout", "refin", "refout"))
-        except (KeyError, TypeError, ValueError):
-            raise _lib.Sy11Error(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
-        if not 8 <= W <= 32 or n_info <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) or refout not in (0, 1) \
-                or (refin and (n_info - W) % 8):
-            raise _lib.Sy11Error(f"{what}: the crc {crc!r} is not of 8 .. 32 bits below n_info = {n_info}, with fields of that width (and whole bytes with refin)")
-        spec = _lib.FecCrc(W, poly, init, xorout, refin, refout)
+    spec = _crc_arg(what, crc, n_info, False, _lib.Sy11Error)
     fr = _fec_frames(what, frames, n)
     bad = fr["T"].astype(np.int64) != n_info + (K - 1) * fr["tail"].astype(np.int64)
     if bad.any():
@@ -1558,7 +1582,7 @@ def fec_check(soft, bits, frames, polys, n_info, data, rows, whiten=None, crc=No
     return data, rows
 
 
-def _rs_table(what, name, t, dtype, dev, n_rows=None, shape=None, least=1):
+def _dev_table(what, name, t, dtype, dev, n_rows=None, shape=None, least=1):
     """A contiguous device table of ``dtype``: 2-D (rows, stride >= least), or of the trailing ``shape``."""
     bad = not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() < 2 or t.shape[0] == 0 or t.shape[0] >= 2 ** 31 or not t.is_contiguous() \
         or (dev is not None and t.device != dev) or (n_rows is not None and t.shape[0] != n_rows)
@@ -1573,8 +1597,7 @@ def _rs_table(what, name, t, dtype, dev, n_rows=None, shape=None, least=1):
 def _rs_args(what, code, interleave, frames, n_rows):
     """The checks the two launches of the frame corrector share (the library repeats them) -> (the ``RsCode``, the int32 table of the frames' rows)."""
     from .data.correct import gf_tables
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))     # noqa: E731
-    if not isinstance(code, dict) or set(code) - {"name"} != {"n", "k", "poly", "fcr", "prim"} or not all(is_int(code[key]) for key in ("n", "k", "poly", "fcr", "prim")):
+    if not isinstance(code, dict) or set(code) - {"name"} != {"n", "k", "poly", "fcr", "prim"} or not all(_is_int(code[key]) for key in ("n", "k", "poly", "fcr", "prim")):
         raise ValueError(f"{what}: `code` must be a dict of the integers n, k, poly, fcr and prim, got {code!r}")
     n, k, poly, fcr, prim = (int(code[key]) for key in ("n", "k", "poly", "fcr", "prim"))
     if not 1 <= k < n <= 255 or n - k > 64:
@@ -1583,18 +1606,10 @@ def _rs_args(what, code, interleave, frames, n_rows):
         raise ValueError(f"{what}: fcr {fcr} is not in [0, 254]")
     if not 1 <= prim <= 254 or math.gcd(prim, 255) != 1:
         raise ValueError(f"{what}: prim {prim} is not in [1, 254] and coprime to 255")
-    if not is_int(interleave) or not 1 <= interleave <= 8:
+    if not _is_int(interleave) or not 1 <= interleave <= 8:
         raise ValueError(f"{what}: interleave {interleave!r} is not in [1, 8]")
     gf_tables(poly, what)                                                       # 9 bits, primitive
-    fr = np.asarray(frames)
-    if fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31 or not np.issubdtype(fr.dtype, np.integer):
-        raise ValueError(f"{what}: `frames` must be a non-empty 1-D integer array of the rows the frames read")
-    row = fr.astype(np.int64)
-    bad = (row < 0) | (row >= n_rows)
-    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
-        i = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
-        raise ValueError(f"{what}: frame {i} reads row {int(row[i])} of a table of {n_rows} rows (a row takes one frame)")
-    return _lib.RsCode(n, k, fcr, prim, int(interleave), poly), np.ascontiguousarray(row.astype(np.int32))
+    return _lib.RsCode(n, k, fcr, prim, int(interleave), poly), _frame_rows(what, frames, n_rows)
 
 
 def rs_decode(data, frames, code, info, cw, interleave=1, offset=0):
@@ -1604,12 +1619,12 @@ def rs_decode(data, frames, code, info, cw, interleave=1, offset=0):
     codeword, and ``cw[row]`` (rows, interleave, 2) int32 the byte errors (-1: not correctable, the bytes pass through) and bit errors of each.  One wavefront
     per codeword.  A refused call raises ``ValueError`` and writes nothing.  -> ``(info, cw)``."""
     what = "rs_decode"
-    _rs_table(what, "data", data, torch.uint8, None)
+    _dev_table(what, "data", data, torch.uint8, None)
     dev, n_rows = data.device, data.shape[0]
     spec, row = _rs_args(what, code, interleave, frames, n_rows)
-    _rs_table(what, "info", info, torch.uint8, dev, n_rows=n_rows, least=spec.interleave * spec.k)
-    _rs_table(what, "cw", cw, torch.int32, dev, n_rows=n_rows, shape=(spec.interleave, 2))
-    if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset < 0 or offset + spec.interleave * spec.n > data.shape[1]:
+    _dev_table(what, "info", info, torch.uint8, dev, n_rows=n_rows, least=spec.interleave * spec.k)
+    _dev_table(what, "cw", cw, torch.int32, dev, n_rows=n_rows, shape=(spec.interleave, 2))
+    if not _is_int(offset) or offset < 0 or offset + spec.interleave * spec.n > data.shape[1]:
         raise ValueError(f"{what}: the {spec.interleave} x {spec.n} bytes at offset {offset!r} leave the {data.shape[1]} bytes of a data row")
     t = torch.from_numpy(row).to(dev)
     call("sy11_rs_decode", row.shape[0], C.c_void_p(row.ctypes.data), _p(t), C.byref(spec), int(offset), n_rows, data.shape[1], _p(data), info.shape[1], _p(info), _p(cw),
@@ -1624,39 +1639,18 @@ def rs_check(info, cw, frames, code, rows, interleave=1, crc=None):
     dict width / poly / init / refin / refout / xorout of whole bytes (``sy11.data.decode.CRCS``), the check field the last bytes, MSB first.  A refused call raises
     ``ValueError`` and writes nothing.  -> ``rows``."""
     what = "rs_check"
-    _rs_table(what, "info", info, torch.uint8, None)
+    _dev_table(what, "info", info, torch.uint8, None)
     dev, n_rows = info.device, info.shape[0]
     spec, row = _rs_args(what, code, interleave, frames, n_rows)
     n_bytes = spec.interleave * spec.k
-    _rs_table(what, "info", info, torch.uint8, dev, least=n_bytes)
-    _rs_table(what, "cw", cw, torch.int32, dev, n_rows=n_rows, shape=(spec.interleave, 2))
-    _rs_table(what, "rows", rows, torch.int32, dev, n_rows=n_rows, shape=(6,))
-    check = _lib.FecCrc()
-    if crc is not None:
-        try:
-            W, poly, init, xorout, refin, refout = (int(crc[key]) for key in ("width", "poly", "init", "xorout", "refin", "refout"))
-        except (KeyError, TypeError, ValueError):
-            raise ValueError(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
-        if W not in (8, 16, 24, 32) or 8 * n_bytes <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) or refout not in (0, 1):
-            raise ValueError(f"{what}: the crc {crc!r} is not of 8, 16, 24 or 32 bits below the {8 * n_bytes} information bits, with fields of that width")
-        check = _lib.FecCrc(W, poly, init, xorout, refin, refout)
+    _dev_table(what, "info", info, torch.uint8, dev, least=n_bytes)
+    _dev_table(what, "cw", cw, torch.int32, dev, n_rows=n_rows, shape=(spec.interleave, 2))
+    _dev_table(what, "rows", rows, torch.int32, dev, n_rows=n_rows, shape=(6,))
+    check = _crc_arg(what, crc, 8 * n_bytes, True, ValueError)
     t = torch.from_numpy(row).to(dev)
     call("sy11_rs_check", row.shape[0], C.c_void_p(row.ctypes.data), _p(t), C.byref(spec), C.byref(check), n_rows, info.shape[1], _p(info), _p(cw), _p(rows), _stream())
     t.record_stream(torch.cuda.current_stream(dev))
     return rows
-
-
-def _ldpc_rows(what, frames, n_rows):
-    """The rows the frames read, each inside the tables and named once -> the contiguous int32 table."""
-    fr = np.asarray(frames)
-    if fr.ndim != 1 or fr.shape[0] == 0 or fr.shape[0] >= 2 ** 31 or not np.issubdtype(fr.dtype, np.integer):
-        raise ValueError(f"{what}: `frames` must be a non-empty 1-D integer array of the rows the frames read")
-    row = fr.astype(np.int64)
-    bad = (row < 0) | (row >= n_rows)
-    if bad.any() or np.unique(row).shape[0] != row.shape[0]:
-        i = _first(bad) if bad.any() else _first(np.bincount(row)[row] > 1)
-        raise ValueError(f"{what}: frame {i} reads row {int(row[i])} of a table of {n_rows} rows (a row takes one frame)")
-    return np.ascontiguousarray(row.astype(np.int32))
 
 
 def _ldpc_call(name, *args):
@@ -1678,20 +1672,19 @@ def ldpc_decode(soft, frames, code, bits, out, post=None, iterations=20, scale=1
     what = "ldpc_decode"
     n_max = _lib.load().sy11_ldpc_nmax()
     cd = _code_of(what, code)
-    _rs_table(what, "soft", soft, torch.int8, None, least=cd.N)
+    _dev_table(what, "soft", soft, torch.int8, None, least=cd.N)
     dev, n_rows = soft.device, soft.shape[0]
-    _rs_table(what, "bits", bits, torch.uint8, dev, n_rows=n_rows, least=(cd.N + 7) // 8)
-    _rs_table(what, "out", out, torch.int32, dev, n_rows=n_rows, shape=(2,))
+    _dev_table(what, "bits", bits, torch.uint8, dev, n_rows=n_rows, least=(cd.N + 7) // 8)
+    _dev_table(what, "out", out, torch.int32, dev, n_rows=n_rows, shape=(2,))
     if post is not None:
-        _rs_table(what, "post", post, torch.int16, dev, n_rows=n_rows, least=cd.N)
+        _dev_table(what, "post", post, torch.int16, dev, n_rows=n_rows, least=cd.N)
     if soft.shape[1] > n_max or bits.shape[1] > n_max // 8 or (post is not None and post.shape[1] > n_max):
         raise ValueError(f"{what}: a row of `soft` / `post` holds at most {n_max} values and one of `bits` {n_max // 8} bytes")
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))     # noqa: E731
-    if not is_int(iterations) or not 1 <= iterations <= 100:
+    if not _is_int(iterations) or not 1 <= iterations <= 100:
         raise ValueError(f"{what}: iterations {iterations!r} is not an integer in [1, 100]")
-    if not is_int(scale) or not 1 <= scale <= 16:
+    if not _is_int(scale) or not 1 <= scale <= 16:
         raise ValueError(f"{what}: scale {scale!r} is not an integer in [1, 16] (sixteenths)")
-    row = _ldpc_rows(what, frames, n_rows)
+    row = _frame_rows(what, frames, n_rows)
     # one upload: the frames' rows, the layers' offsets, the entries
     layer, entry = np.ascontiguousarray(cd.layer, dtype=np.int32), np.ascontiguousarray(cd.entry)
     host = np.concatenate((row, layer, entry.view(np.int32)))
@@ -1713,32 +1706,20 @@ def ldpc_check(soft, bits, frames, N, K, data, rows, whiten=None, crc=None):
     -> ``(data, rows)``."""
     what = "ldpc_check"
     n_max = _lib.load().sy11_ldpc_nmax()
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))     # noqa: E731
-    if not is_int(N) or not is_int(K) or not 2 <= N <= n_max or N % 2 or not 1 <= K < N:
+    if not _is_int(N) or not _is_int(K) or not 2 <= N <= n_max or N % 2 or not 1 <= K < N:
         raise ValueError(f"{what}: N = {N!r} is not an even integer in [2, {n_max}], or K = {K!r} not an integer in [1, N)")
     N, K = int(N), int(K)
-    _rs_table(what, "soft", soft, torch.int8, None, least=N)
+    _dev_table(what, "soft", soft, torch.int8, None, least=N)
     dev, n_rows = soft.device, soft.shape[0]
-    _rs_table(what, "bits", bits, torch.uint8, dev, n_rows=n_rows, least=(N + 7) // 8)
-    _rs_table(what, "data", data, torch.uint8, dev, n_rows=n_rows, least=(K + 7) // 8)
-    _rs_table(what, "rows", rows, torch.int32, dev, n_rows=n_rows, shape=(5,))
+    _dev_table(what, "bits", bits, torch.uint8, dev, n_rows=n_rows, least=(N + 7) // 8)
+    _dev_table(what, "data", data, torch.uint8, dev, n_rows=n_rows, least=(K + 7) // 8)
+    _dev_table(what, "rows", rows, torch.int32, dev, n_rows=n_rows, shape=(5,))
     if soft.shape[1] > n_max or bits.shape[1] > n_max // 8 or data.shape[1] > n_max // 8:
         raise ValueError(f"{what}: a row of `soft` holds at most {n_max} values and one of `bits` / `data` {n_max // 8} bytes")
     if whiten is not None:
-        try:
-            _u8_vector(what, "whiten", whiten, dev, K)
-        except _lib.Sy11Error as e:
-            raise ValueError(str(e)) from None
-    spec = _lib.FecCrc()
-    if crc is not None:
-        try:
-            W, poly, init, xorout, refin, refout = (int(crc[k]) for k in ("width", "poly", "init", "xorout", "refin", "refout"))
-        except (KeyError, TypeError, ValueError):
-            raise ValueError(f"{what}: `crc` must be None or a dict of width, poly, init, refin, refout and xorout") from None
-        if not 8 <= W <= 32 or K <= W or not all(0 <= v < 2 ** W for v in (poly, init, xorout)) or refin not in (0, 1) or refout not in (0, 1) or (refin and (K - W) % 8):
-            raise ValueError(f"{what}: the crc {crc!r} is not of 8 .. 32 bits below K = {K}, with fields of that width (and whole bytes with refin)")
-        spec = _lib.FecCrc(W, poly, init, xorout, refin, refout)
-    row = _ldpc_rows(what, frames, n_rows)
+        _u8_vector(what, "whiten", whiten, dev, K, ValueError)
+    spec = _crc_arg(what, crc, K, False, ValueError)
+    row = _frame_rows(what, frames, n_rows)
     t = torch.from_numpy(row).to(dev)
     _ldpc_call("sy11_ldpc_check", row.shape[0], C.c_void_p(row.ctypes.data), _p(t), N, K, _p(whiten), C.byref(spec), n_rows, soft.shape[1], _p(soft), bits.shape[1], _p(bits),
                data.shape[1], _p(data), _p(rows), _stream())

@@ -1,7 +1,8 @@
 """GPU: the frame corrector's kernels (sy11_rs_decode, sy11_rs_check) against tests/_rs_ref.py.  Every comparison is ``np.array_equal``: the decoder is exact
 integer arithmetic.  The kernel-level tests feed synthetic byte rows to ``ops.rs_*`` directly, for every preset and four more codes, every interleaving depth
 and offset, with the outputs' slack and spare rows filled with sentinels that must survive; one call over all frames, one call per frame and a permuted
-packing give the same bytes; every refusal is raised by ``ops`` and by the library with the outputs untouched; and ``demodulate`` -> ``find_frames`` -> ``decode``
+packing give the same bytes; the byte-serial CRC of ``rs_check`` and the bit-serial one of ``fec_check`` / ``ldpc_check`` agree on the same bytes; every refusal is raised by ``ops``
+and by the library with the outputs untouched; and ``demodulate`` -> ``find_frames`` -> ``decode``
 -> ``correct`` on two clips reads what was sent, through a burst the Viterbi decoder does not survive, in exactly two launches."""
 import copy
 import ctypes as C
@@ -197,6 +198,52 @@ def test_check_sums_and_crc_over_the_corrected_bytes(name):
         assert got[f, :3].tolist() == want[:3] and got[f, 3:5].view(np.uint32).tolist() == want[3:5] and got[f, 5] == want[5], (name, f)
         assert want[0] == (1 if f == 4 else 0) and want[5] == (-1 if spec is None else int(f < 3))
         assert want[1] == sum(int(e) for e in cw[f, :, 0] if e >= 0) and want[1] > 0
+
+
+def test_bit_serial_and_byte_serial_crc_agree_in_the_three_check_launches():
+    """The one CRC of csrc/frame_check.h in its two forms: ``ops.fec_check`` and ``ops.ldpc_check`` run it bit by bit, ``ops.rs_check`` byte by byte.  The same information
+    bytes (a message and its check field) go to all three, for every whole-byte spec: the three (crc_calc, crc_recv, crc_ok) are identical and those of
+    tests/_fec_ref.crc; one flipped message bit in frame 1 and all three say crc_ok = 0 there."""
+    from sy11 import ops
+    from sy11.data.decode import FECFRAME
+    specs = dict(FEC.CRCS, **{"crc24-refin": dict(width=24, poly=0x864CFB, init=0xB704CE, refin=True, refout=False, xorout=0x000000)})
+    msgs = [np.frombuffer(b"123456789", dtype=np.uint8).copy(), np.random.default_rng(45).integers(0, 256, 9).astype(np.uint8)]
+    up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype)      # noqa: E731
+    for name, spec in specs.items():
+        W = spec["width"]
+        k, n_info = 9 + W // 8, 8 * (9 + W // 8)
+        for flip in (False, True):
+            body = [m.copy() for m in msgs]
+            field = [FEC.crc(np.unpackbits(m), spec) for m in msgs]             # the check field of the message as it was sent
+            if flip:
+                body[1][4] ^= 0x10
+            info = np.stack([np.concatenate((m, [(c >> (W - 8 - 8 * i)) & 255 for i in range(W // 8)])).astype(np.uint8) for m, c in zip(body, field)])
+            want = [[FEC.crc(np.unpackbits(m), spec), c, int(FEC.crc(np.unpackbits(m), spec) == c)] for m, c in zip(body, field)]
+            got = {}
+            # the Viterbi decoder's check: no tail, T = n_info steps, the decided bits are the information
+            fr = np.zeros(2, dtype=FECFRAME)
+            fr["T"], fr["order"], fr["row"], fr["scale"] = n_info, 2, np.arange(2), 1.0
+            rows = torch.full((2, 5), CW_FILL, dtype=torch.int32, device=DEV)
+            data = torch.full((2, k), DATA_FILL, dtype=torch.uint8, device=DEV)
+            ops.fec_check(torch.zeros((2, 2 * n_info), dtype=torch.int8, device=DEV), up(info, torch.uint8), fr, FEC.POLYS, n_info, data, rows, crc=spec)
+            got["fec_check"] = rows.cpu().numpy()[:, :3]
+            assert np.array_equal(data.cpu().numpy(), info)
+            # the LDPC decoder's check: N = K + 2, the first K decided bits are the information
+            rows = torch.full((2, 5), CW_FILL, dtype=torch.int32, device=DEV)
+            data = torch.full((2, k), DATA_FILL, dtype=torch.uint8, device=DEV)
+            decided = np.concatenate((info, np.zeros((2, 1), dtype=np.uint8)), axis=1)
+            ops.ldpc_check(torch.zeros((2, n_info + 2), dtype=torch.int8, device=DEV), up(decided, torch.uint8), np.arange(2), n_info + 2, n_info, data, rows, crc=spec)
+            got["ldpc_check"] = rows.cpu().numpy()[:, :3]
+            assert np.array_equal(data.cpu().numpy(), info)
+            # the corrector's check: one codeword of k information bytes, nothing corrected
+            rows = torch.full((2, 6), CW_FILL, dtype=torch.int32, device=DEV)
+            ops.rs_check(up(info, torch.uint8), torch.zeros((2, 1, 2), dtype=torch.int32, device=DEV), np.arange(2), R.code(k + 2, k), rows, interleave=1, crc=spec)
+            got["rs_check"] = rows.cpu().numpy()[:, 3:]
+            for launch, r in got.items():
+                calc, recv, ok = r[:, 0].copy().view(np.uint32).tolist(), r[:, 1].copy().view(np.uint32).tolist(), r[:, 2].tolist()
+                assert [list(t) for t in zip(calc, recv, ok)] == want, (name, flip, launch)
+            assert [w[2] for w in want] == [1, 0 if flip else 1], (name, flip)
+    assert FEC.crc(np.unpackbits(msgs[0]), specs["crc32"]) == 0xCBF43926
 
 
 # ------------------------------------------------------------------------------------------------------------- refusals
