@@ -748,6 +748,69 @@ int sy11_demod_symbols(int32_t n_item, const sy11_demod_block* item_host, const 
 int sy11_demod_decide(int32_t n_item, const sy11_demod_dec* item_host, const sy11_demod_dec* item, int64_t n_sym, const float* sym,
                       int64_t n_rows, const double* theta, float* r, uint8_t* d, double* rows, void* stream);
 
+/* ---- frequency-keyed demodulation: 2-FSK / GFSK / GMSK clips of an extraction by their discriminator (spec in DESIGN.md §4) ----
+ * Feed-forward, three launches over all clips; the two fits between them are the caller's (sy11/data/demodulate_fsk.py).  The result has the
+ * shape of the demodulation's at order 2: real symbols around +-1, stored as complex64 with a zero imaginary part.
+ *
+ * Launch 1, sy11_iq_fsk_filter.  An item is one tile of TILE = the value of sy11_iq_demod_tile usable samples [n0  n0 + cnt) of the clip
+ * in[off  off + len): the usable span is [hw + 1  len - hw), n0 - hw - 1 a multiple of TILE, cnt = TILE except on the clip's last tile.
+ *   f[n] = arg(in[n] conj(in[n - 1]) e^{-2 pi i wc 2^-64}) / 2 pi  (cycles per sample, 1 <= n < len)     y[n] = sum_{|k| <= hw} f[n - k] taps[tap_off + hw + k]
+ * in float64 (f once per sample, the taps ascending in -k, fused multiply-adds) and rounded ONCE to the float32 written to y[off + n] for the item's usable
+ * samples; the item with first = 1 also writes the zeros of y[off  off + hw + 1), the item with last = 1 those of y[off + len - hw  off + len): the items of a clip
+ * write every y[n] of the clip once.  Per item, with w[n] = e^{-2 pi i (n ws mod 2^64) 2^-64},
+ *   rows[row 8 + 0 .. 7] = Re, Im of sum y^2 w;  Re, Im of sum y w;  Re, Im of sum w;  sum y;  sum y^2     over its usable samples
+ * in float64 from the stored float32 y.  item: DEVICE table, item_host: its HOST copy, checked entry by entry before anything is launched:
+ * the clip lies inside in[0  n_in), n_taps = 2 hw + 1 <= 513 taps lie inside taps[0  n_tap), the tile is a tile of the usable span,
+ * first / last say what they must, and every row of rows[0  n_rows 8) is written by one item.  in: packed complex64 (a clip may start at an
+ * odd sample), y: n_in float32, packed like in.  One fixed order for every sum; no atomics.  Nothing is launched on an error.
+ *
+ * Launch 2, sy11_fsk_symbols.  An item is 1 .. 256 consecutive symbols of one clip: symbol i sits at t0 + i step = (k + mu) 2^32
+ * (Q32.32, mu cut to its top 24 bits) and is the 4-point cubic Lagrange interpolation of y[off + k - 1 .. k + 2] at mu, in float64 and rounded once, written
+ * to sym[sym_off + i] (float32).  rows[row 4 + 0 .. 3] = the number of s_i >= m, their sum, the sum of the s_i < m, and sum s_i^2, float64 from the stored s.
+ * Checked: 1 <= k <= len - 3 for every symbol, 2^32 <= step <= 2^40, the symbols inside sym[0  n_sym), m finite, one item per row.
+ *
+ * Launch 3, sy11_fsk_decide.  An item is 1 .. 256 consecutive symbols sym[sym_off  sym_off + n):  r_i = (s_i - f0) / dev in float64, rounded once to
+ * float32 -> r[2 (sym_off + i)] with r[2 (sym_off + i) + 1] = 0;  d[sym_off + i] = (r_i < 0);  rows[row 3 + 0 .. 2] = sum r^2, sum |r|, n (the columns
+ * of sy11_demod_decide at order 2).  Checked: the symbols inside sym[0  n_sym) (r: n_sym complex64, d: n_sym bytes), f0 finite, dev finite and > 0,
+ * one item per row.                                                                                                              */
+typedef struct sy11_fsk_item {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip                                                              */
+  int64_t n0;                  /* first usable sample of the tile (index in the clip)                              */
+  int64_t tap_off;             /* first tap of the clip in the tap buffer                                          */
+  uint64_t wc;                 /* carrier: cycles per sample 2^64, wrapping                                        */
+  uint64_t ws;                 /* symbol rate: cycles per sample 2^64                                              */
+  int32_t cnt;                 /* usable samples of the tile, 1 .. TILE                                            */
+  int32_t hw;                  /* half width of the filter                                                         */
+  int32_t n_taps;              /* 2 hw + 1                                                                         */
+  int32_t row;                 /* row of the table the item writes                                                 */
+  int32_t first;               /* 1: the clip's first tile, which also zeroes y[0  hw + 1); else 0                 */
+  int32_t last;                /* 1: the clip's last tile, which also zeroes y[len - hw  len); else 0              */
+} sy11_fsk_item;
+typedef struct sy11_fsk_block {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip                                                              */
+  int64_t t0;                  /* position of the item's first symbol, Q32.32 samples from the clip's first        */
+  int64_t step;                /* samples per symbol, Q32.32                                                       */
+  int64_t sym_off;             /* the item's first symbol in the packed symbol buffer                              */
+  double m;                    /* the clip's mean of y: the level that splits the two tones                        */
+  int32_t n;                   /* symbols, 1 .. 256                                                                */
+  int32_t row;                 /* row of the table the item writes                                                 */
+} sy11_fsk_block;
+typedef struct sy11_fsk_dec {
+  int64_t sym_off;             /* the item's first symbol in the packed symbol buffer                              */
+  double f0;                   /* the clip's level midpoint, cycles per sample                                     */
+  double dev;                  /* the clip's deviation, cycles per sample, > 0                                     */
+  int32_t n;                   /* symbols, 1 .. 256                                                                */
+  int32_t row;                 /* row of the table the item writes                                                 */
+} sy11_fsk_dec;
+int sy11_iq_fsk_filter(int32_t n_item, const sy11_fsk_item* item_host, const sy11_fsk_item* item, int64_t n_tap, const float* taps,
+                       int64_t n_in, const float* in, float* y, int64_t n_rows, double* rows, void* stream);
+int sy11_fsk_symbols(int32_t n_item, const sy11_fsk_block* item_host, const sy11_fsk_block* item, int64_t n_in, const float* y,
+                     int64_t n_sym, float* sym, int64_t n_rows, double* rows, void* stream);
+int sy11_fsk_decide(int32_t n_item, const sy11_fsk_dec* item_host, const sy11_fsk_dec* item, int64_t n_sym, const float* sym, float* r,
+                    uint8_t* d, int64_t n_rows, double* rows, void* stream);
+
 /* ---- frame search: where the sync words sit in the corrected symbols of every clip, and at which rotation (spec in DESIGN.md §4) ----
  * Three launches over all clips; between the second and the third the caller compacts the hits (sy11/data/frames.py).  sym: the packed
  * corrected symbols (complex64, what sy11_demod_decide wrote to r); words: packed DECISIONS of the words, one byte per symbol as d of

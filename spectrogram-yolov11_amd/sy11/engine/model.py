@@ -367,6 +367,13 @@ class YOLO:
         return demodulate_extraction(extraction, characterization, symbol_rate=symbol_rate, offset=offset, order=order, beta=beta, span=span,
                                      block=block)
 
+    def demodulate_fsk(self, extraction, *, symbol_rate, offset=0.0, pulse="gauss", bt=0.5, span=2, block=32):
+        """Demodulate every frequency-keyed clip (2-FSK, GFSK, GMSK) of ``extraction`` on the GPU -> ``sy11.data.demodulate_fsk.FskDemodulation``: a
+        ``Demodulation`` at order 2 with real symbols around +-1, the decisions, the error-vector magnitude, the midpoint of the two tones and their
+        deviation, from the caller's ``symbol_rate`` and ``offset`` (``DetectionPredictor.demodulate_fsk``)."""
+        from ..data.demodulate_fsk import demodulate_fsk_extraction
+        return demodulate_fsk_extraction(extraction, symbol_rate=symbol_rate, offset=offset, pulse=pulse, bt=bt, span=span, block=block)
+
     def find_frames(self, demodulation, words, *, payload=0, threshold=0.8, max_errors=None, t0=None):
         """Find the sync ``words`` in every clip of ``demodulation`` on the GPU -> ``sy11.data.frames.Frames``: per frame its clip, word, position, the
         rotation that resolves the demodulator's phase ambiguity, the word's errors and ``payload`` symbols' bits

@@ -306,6 +306,23 @@ class DetectionPredictor:
         return demodulate_extraction(extraction, characterization, symbol_rate=symbol_rate, offset=offset, order=order, beta=beta, span=span,
                                      block=block)
 
+    def demodulate_fsk(self, extraction, *, symbol_rate, offset=0.0, pulse="gauss", bt=0.5, span=2, block=32):
+        """Read every frequency-keyed clip (2-FSK, GFSK, GMSK) of ``extraction`` (what ``extract`` returned) by its discriminator ->
+        ``sy11.data.demodulate_fsk.FskDemodulation``, a ``Demodulation`` at order 2 that ``find_frames``, ``equalize``, ``decode``, ``decode_ldpc`` and ``correct`` take as it is
+        (``csrc/demod_fsk.hip``).  ``symbol_rate`` and ``offset`` (Hz from the clip's centre, a first guess of the midpoint of the two tones) come from the
+        caller, per clip or as scalars, as do ``pulse``, ``bt`` and ``span``.  All clips go through THREE launches: the instantaneous frequency ``arg(x[n] conj(x[n - 1])) / 2 pi`` of every
+        sample, filtered by a Gaussian of bandwidth-time product ``bt`` over ``span`` symbols each side (``pulse="gauss"``) or by an integrate-and-dump
+        over one symbol (``pulse="rect"``), with the timing partials of every 512-sample tile; the symbols, interpolated at the instants of a line
+        fitted through the tiles' timing phases, with the sums of the two levels per ``block`` symbols; the symbols scaled so that the two tones
+        sit at +-1, and the decisions.  ``carrier_fit`` is the midpoint of the two tones, ``deviation`` half their distance (Hz), ``mod_index`` their
+        distance over the symbol rate.  Which tone is "1" is not known (``phase_ambiguity`` 2): ``find_frames``' rotation 1 is the inverted polarity.
+        A clip that cannot be demodulated (2.5 <= fs / symbol_rate <= 16 violated, |offset| >= fs / 2, too short, one tone only) is a row with
+        ``valid`` False and a ``reason``.  Not done here: a pre-detection filter (``extract``'s low-pass is the one), 4-FSK, estimating the symbol rate
+        (``characterize`` calls a constant-envelope clip "not keyed"), coherent MSK detection, a carrier that drifts over the clip.  Argument errors
+        are ``ValueError``s raised before anything touches the device; without a valid clip nothing is launched."""
+        from ..data.demodulate_fsk import demodulate_fsk_extraction
+        return demodulate_fsk_extraction(extraction, symbol_rate=symbol_rate, offset=offset, pulse=pulse, bt=bt, span=span, block=block)
+
     def find_frames(self, demodulation, words, *, payload=0, threshold=0.8, max_errors=None, t0=None):
         """Say where framed data starts in every clip of ``demodulation`` (what ``demodulate`` returned) and at which of the ``order`` rotations the
         demodulator landed -> ``sy11.data.frames.Frames``, one row per frame sorted by (clip, word, position) (``csrc/framesync.hip``).  ``words``: the

@@ -1072,6 +1072,153 @@ def demod_decide(sym, items, theta, r, d, rows):
     return r, d, rows
 
 
+def _packed_f32(what, name, v, dev, n=None):
+    if v.dtype != torch.float32 or v.dim() != 1 or not v.is_contiguous() or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or v.data_ptr() % 4 or v.device != dev \
+            or (n is not None and v.shape[0] != n):
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty 1-D contiguous float32 tensor below 2^31 on the input's device" + ("" if n is None else f" of {n} entries"))
+
+
+def _rows_of(what, name, v, dev, width):
+    if v.dtype != torch.float64 or v.dim() != 2 or v.shape[1] != width or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or not v.is_contiguous() or v.device != dev \
+            or v.data_ptr() % 8:
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty contiguous (rows, {width}) float64 tensor on the input's device")
+
+
+def iq_fsk_filter(x, items, taps, y, rows):
+    """Launch 1 of the frequency-keyed demodulation (sy11_iq_fsk_filter): every item of ``items`` — ``sy11.data.demodulate_fsk.ITEM`` records (off, len,
+    n0, tap_off, wc, ws, cnt, hw, n_taps, row, first, last): the tile ``[n0, n0 + cnt)`` of the usable span ``[hw + 1, len - hw)`` of the clip
+    ``x[off : off + len]`` — takes the discriminator of its samples (turned back by ``wc``), filters it with ``taps[tap_off : tap_off + n_taps]`` into ``y``
+    (float32, packed like ``x``) and writes the eight sums at ``ws`` to ``rows[row]`` (rows, 8) f64.  ``x``: the packed clips, 1-D contiguous complex64; a
+    clip may start at an odd sample.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``(y, rows)``."""
+    from .data.demodulate import MAX_TAPS
+    from .data.demodulate_fsk import ITEM
+    what = "iq_fsk_filter"
+    _need_gpu(x, taps, y, rows)
+    _packed_c64(what, "x", x)
+    _packed_f32(what, "y", y, x.device, x.shape[0])
+    _rows_of(what, "rows", rows, x.device, 8)
+    if taps.dtype != torch.float32 or taps.dim() != 1 or taps.shape[0] == 0 or taps.shape[0] >= 2 ** 31 or not taps.is_contiguous() or taps.device != x.device \
+            or taps.data_ptr() % 4:
+        raise _lib.Sy11Error(f"{what}: `taps` must be a non-empty 1-D contiguous float32 tensor on x's device")
+    it = np.ascontiguousarray(items)
+    if it.dtype != ITEM or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.demodulate_fsk.ITEM records")
+    T, n_in, n_tap = _lib.load().sy11_iq_demod_tile(), x.shape[0], taps.shape[0]
+    off, ln, n0, tap_off = it["off"], it["len"], it["n0"], it["tap_off"]
+    cnt, hw, n_taps, row = (it[k].astype(np.int64) for k in ("cnt", "hw", "n_taps", "row"))
+    bad = (off < 0) | (ln < 1) | (ln > n_in) | (off > n_in - ln)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: the clip [{int(off[k])}, {int(off[k] + ln[k])}) leaves the {n_in} packed samples")
+    bad = (hw < 1) | (n_taps != 2 * hw + 1) | (n_taps > MAX_TAPS)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: {int(n_taps[k])} taps for a half width of {int(hw[k])} (odd, 2 hw + 1, at most {MAX_TAPS})")
+    bad = (tap_off < 0) | (tap_off > n_tap - n_taps)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: taps [{int(tap_off[k])}, {int(tap_off[k] + n_taps[k])}) leave the {n_tap} packed taps")
+    bad = (n0 < hw + 1) | ((n0 - hw - 1) % T != 0) | (cnt < 1) | (cnt > T) | (n0 > ln - hw - cnt)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: samples [{int(n0[k])}, {int(n0[k] + cnt[k])}) are not a tile of the usable span [{int(hw[k]) + 1}, {int(ln[k] - hw[k])})")
+    bad = it["first"] != (n0 == hw + 1)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: first = {int(it['first'][k])}, but it starts at {int(n0[k])} of the usable span from {int(hw[k]) + 1}")
+    is_last = n0 + cnt == ln - hw
+    bad = (it["last"] != is_last) | (~is_last & (cnt != T))
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: last = {int(it['last'][k])} with {int(cnt[k])} samples, but it ends at {int(n0[k] + cnt[k])} of the usable span "
+                             f"to {int(ln[k] - hw[k])}")
+    _one_item_per_row(what, row, rows.shape[0])
+    t = torch.from_numpy(it.view(np.uint8)).to(x.device)
+    call("sy11_iq_fsk_filter", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_tap, _p(taps), n_in,
+         C.c_void_p(torch.view_as_real(x).data_ptr()), _p(y), rows.shape[0], _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return y, rows
+
+
+def fsk_symbols(y, items, sym, rows):
+    """Launch 2 of the frequency-keyed demodulation (sy11_fsk_symbols): every item of ``items`` — ``sy11.data.demodulate_fsk.BLOCK`` records (off, len, t0,
+    step, sym_off, m, n, row): ``n`` (1 .. 256) symbols of the clip ``y[off : off + len]`` at the Q32.32 positions ``t0 + i step`` — writes the cubic
+    interpolation of ``y`` (float32) at every position to ``sym[sym_off + i]`` (float32) and the count and sum of the symbols at or above ``m``, the sum
+    of those below and the sum of squares to ``rows[row]`` (rows, 4) f64.  A refused call raises ``Sy11Error`` and writes nothing.  -> ``(sym, rows)``."""
+    from .data.demodulate_fsk import BLOCK
+    what = "fsk_symbols"
+    _need_gpu(y, sym, rows)
+    _packed_f32(what, "y", y, y.device)
+    _packed_f32(what, "sym", sym, y.device)
+    _rows_of(what, "rows", rows, y.device, 4)
+    if sym.data_ptr() == y.data_ptr():
+        raise _lib.Sy11Error(f"{what}: `sym` may not be y")
+    it = np.ascontiguousarray(items)
+    if it.dtype != BLOCK or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.demodulate_fsk.BLOCK records")
+    n_in, n_sym = y.shape[0], sym.shape[0]
+    off, ln, t0, step, sym_off = it["off"], it["len"], it["t0"], it["step"], it["sym_off"]
+    n, row = (it[k].astype(np.int64) for k in ("n", "row"))
+    bad = (off < 0) | (ln < 4) | (ln > n_in) | (off > n_in - ln)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: the clip [{int(off[k])}, {int(off[k] + ln[k])}) leaves the {n_in} packed samples")
+    bad = (n < 1) | (n > 256) | (sym_off < 0) | (sym_off > n_sym - n)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: symbols [{int(sym_off[k])}, {int(sym_off[k] + n[k])}) are not 1 .. 256 of the {n_sym} packed symbols")
+    bad = (step < 2 ** 32) | (step > 2 ** 40) | (t0 < 2 ** 32) | (t0 >= ln * 2 ** 32)
+    bad = bad | (((t0 + (n - 1) * np.where(bad, 0, step)) >> 32) > ln - 3)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: positions from {int(t0[k])} in steps of {int(step[k])} (Q32.32) leave [1, {int(ln[k]) - 3}]")
+    bad = ~np.isfinite(it["m"])
+    if bad.any():
+        raise _lib.Sy11Error(f"{what}: item {_first(bad)}: the mean m is not finite")
+    _one_item_per_row(what, row, rows.shape[0])
+    t = torch.from_numpy(it.view(np.uint8)).to(y.device)
+    call("sy11_fsk_symbols", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_in, _p(y), n_sym, _p(sym), rows.shape[0], _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(y.device))
+    return sym, rows
+
+
+def fsk_decide(sym, items, r, d, rows):
+    """Launch 3 of the frequency-keyed demodulation (sy11_fsk_decide): every item of ``items`` — ``sy11.data.demodulate_fsk.DEC`` records (sym_off, f0, dev,
+    n, row): ``n`` (1 .. 256) symbols from ``sym[sym_off]`` (float32) — writes ``(s - f0) / dev`` to ``r`` (complex64 of ``sym``'s length, the imaginary part
+    zero), the decisions ``r < 0`` to ``d`` (uint8) and the sums of ``r^2``, ``|r|`` and the count to ``rows[row]`` (rows, 3) f64.  A refused call raises
+    ``Sy11Error`` and writes nothing.  -> ``(r, d, rows)``."""
+    from .data.demodulate_fsk import DEC
+    what = "fsk_decide"
+    _need_gpu(sym, r, d, rows)
+    _packed_f32(what, "sym", sym, sym.device)
+    _packed_c64(what, "r", r)
+    if r.device != sym.device or r.shape != sym.shape:
+        raise _lib.Sy11Error(f"{what}: `r` must be a ({sym.shape[0]},) complex64 tensor on sym's device")
+    _row_table(what, "rows", rows, sym.device)
+    if d.dtype != torch.uint8 or tuple(d.shape) != tuple(sym.shape) or not d.is_contiguous() or d.device != sym.device:
+        raise _lib.Sy11Error(f"{what}: `d` must be a contiguous ({sym.shape[0]},) uint8 tensor on sym's device")
+    it = np.ascontiguousarray(items)
+    if it.dtype != DEC or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise _lib.Sy11Error(f"{what}: `items` must be a non-empty 1-D array of sy11.data.demodulate_fsk.DEC records")
+    n_sym, n_rows = sym.shape[0], rows.shape[0]
+    sym_off, f0, dv = it["sym_off"], it["f0"], it["dev"]
+    n, row = (it[k].astype(np.int64) for k in ("n", "row"))
+    bad = (n < 1) | (n > 256) | (sym_off < 0) | (sym_off > n_sym - n)
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: symbols [{int(sym_off[k])}, {int(sym_off[k] + n[k])}) are not 1 .. 256 of the {n_sym} packed symbols")
+    bad = ~(np.isfinite(f0) & np.isfinite(dv) & (dv > 0))
+    if bad.any():
+        k = _first(bad)
+        raise _lib.Sy11Error(f"{what}: item {k}: f0 = {float(f0[k])}, dev = {float(dv[k])}: both must be finite and dev positive")
+    _one_item_per_row(what, row, n_rows)
+    t = torch.from_numpy(it.view(np.uint8)).to(sym.device)
+    call("sy11_fsk_decide", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), n_sym, _p(sym), C.c_void_p(torch.view_as_real(r).data_ptr()),
+         _p(d), n_rows, _p(rows), _stream())
+    t.record_stream(torch.cuda.current_stream(sym.device))
+    return r, d, rows
+
+
 def _u8_vector(what, name, v, dev, n=None, exc=_lib.Sy11Error):
     if v.dtype != torch.uint8 or v.dim() != 1 or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or not v.is_contiguous() or v.device != dev \
             or (n is not None and v.shape[0] != n):
