@@ -59,6 +59,8 @@ const char* sy11_last_error(void);
  *   "dgrad_s2_halo" 0|1 (3x3 stride-2 input gradient: four igemm launches, one per output parity / ONE fused-parity pass),
  *   "row_map" 0|1 (row walk of the BatchNorm and copy kernels: strided grid of r01 / contiguous chunk per workgroup),
  *   "maxpool_sep" 0|1 (5x5 max-pool of 16-bit tensors with 16-byte channel vectors: 25-way kernels / separable forward and column-walk backward),
+ *   "dwgrad_fused" 0|1 (large-map dense 1x1 layers: input + filter gradient as the pair / as sy11_conv2d_dgrad_wgrad_1x1, read by the engine),
+ *   "dwgrad_wg" n (workgroups per column block of sy11_conv2d_dgrad_wgrad_1x1; 0 = one resident round),
  *   "deterministic" 0|1   ordered reductions (cfg/default.yaml:29 `deterministic: True`, utils/torch_utils.py:474-492): every sum
  *                         across workgroups — BatchNorm statistics and backward sums, filter / bias gradients, loss partials —
  *                         goes through one partial row per workgroup and a fixed-shape fold instead of f32 atomics; bit-identical
@@ -66,15 +68,16 @@ const char* sy11_last_error(void);
  *                         rows live in a per-stream workspace the LIBRARY allocates (grown during eager warm-up, never under capture).
  *                         Cost on the headline workload: +3.8 ... +4.9 % per training step (r04).
  * Defaults come from the environment (SY11_TUNE, SY11_TUNE_LOG, SY11_IGEMM_CFG, SY11_WGRAD_CFG, SY11_IGEMM_KORDER,
- * SY11_IGEMM_DEEP, SY11_IGEMM_BPOL, SY11_DGRAD_S2_HALO, SY11_ROW_MAP, SY11_DETERMINISTIC, SY11_MAXPOOL_SEP).  Process-wide; set them between
+ * SY11_IGEMM_DEEP, SY11_IGEMM_BPOL, SY11_DGRAD_S2_HALO, SY11_ROW_MAP, SY11_DETERMINISTIC, SY11_MAXPOOL_SEP,
+ * SY11_DWGRAD_FUSED, SY11_DWGRAD_WG).  Process-wide; set them between
  * launches, not concurrently with them.                                                                                */
 int sy11_set_option(const char* name, int32_t value);
 int sy11_get_option(const char* name, int32_t* value);
 /* Two more names are READ-ONLY (sy11_get_option answers, sy11_set_option fails with a message): igemm_last_cfg and wgrad_last_cfg,
  * the tile configuration of the most recent forward / input-gradient launch and of the most recent filter-gradient launch
  * (csrc/igemm.hip 0..25, csrc/wgrad.hip 0..19; 100 = the fused-parity stride-2 input gradient, which is no entry of the igemm
- * table, and in wgrad_last_cfg the grouped launch of sy11_conv2d_wgrad_group, which is no entry of the wgrad table; -1 before the
- * first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.
+ * table, and in wgrad_last_cfg the grouped launch of sy11_conv2d_wgrad_group, which is no entry of the wgrad table, 101 there the fused 1x1 launch of
+ * sy11_conv2d_dgrad_wgrad_1x1; -1 before the first launch).  The tuner's candidate launches record themselves too: read them with "tune" 0.
  * Likewise stem_fwd_last and stem_wgrad_last: which first-layer kernel (csrc/direct.hip) the most recent sy11_stem_conv_fwd[_bn] /
  * sy11_stem_conv_wgrad launched — 1 gather, 2 MFMA gather, 3 LDS-tiled with 16-byte image loads, 4 LDS-tiled with element-wise
  * fill; -1 before the first launch.
@@ -168,6 +171,26 @@ int sy11_conv2d_wgrad_group(int32_t dtype, int32_t count, const sy11_wgrad_probl
  * workgroups wg_start[i] .. wg_start[i+1] (count + 1 entries), tiles_i * ceil(M / pix_per_split[i]) of them, split-major.       */
 int sy11_wgrad_group_plan(int32_t count, const int32_t* M, const int32_t* N, const int32_t* K, int32_t target_workgroups,
                           int32_t* pix_per_split, int32_t* wg_start);
+
+/* Input gradient and filter gradient of a DENSE 1x1 / stride-1 / unpadded convolution in one launch: dy is read once instead of
+ * once per gradient (csrc/dwgrad1x1.hip).  M = B*H*W pixels, C input and N output channels;
+ *     dx[m][c]  = sum_n dy[m][n] * wt[c][n]   (dx += ... when accumulate != 0; dx has the dtype of dy)
+ *     dw[n][c] += sum_m dy[m][n] * x[m][c]    (f32, f32 atomics: zero it for a fresh gradient)
+ * — what sy11_conv2d_dgrad followed by sy11_conv2d_wgrad compute for that layer, up to summation order.  dtype F16 or BF16 (F32:
+ * SY11_EUNSUPPORTED); C and N multiples of 16 in 16..256 (else SY11_EUNSUPPORTED); dy, x, dx are pixel-major views with pixel strides
+ * dy_ld >= N, x_ld >= C, dx_ld >= C (multiples of 8, 16-byte aligned bases, each view below 2 GiB): channel slices of wider tensors
+ * work, the channels outside a slice are not touched.  wt: the [C][N] filter of sy11_weight_transpose.  With the "deterministic"
+ * option on the call returns SY11_EUNSUPPORTED and launches nothing (the caller runs the pair, which has the ordered path).
+ * Persistent workgroups, one resident round by the occupancy API ("dwgrad_wg" n > 0 forces n workgroups per column block);
+ * "wgrad_last_cfg" reads 101 after the launch.  "dwgrad_fused" (SY11_DWGRAD_FUSED, default 1) is the ENGINE's switch between this
+ * entry point and the pair; the entry point does not look at it.                                                              */
+int sy11_conv2d_dgrad_wgrad_1x1(int32_t dtype, int32_t M, int32_t C, int32_t N, const void* dy, int32_t dy_ld, const void* x,
+                                int32_t x_ld, const void* wt, void* dx, int32_t dx_ld, int32_t accumulate, float* dw, void* stream);
+/* The tile choice of that launch, host arithmetic only: np = N rounded up to 64 / 128 / 256; the widest column block of 256 / 128 /
+ * 64 input channels with np * block <= 32768 whose LDS image, 256 * (np + block) + 2 * np * block bytes, fits lds_bytes;
+ * blocks = ceil(C / that), cb = ceil(C / blocks) rounded up to 16, cp = cb rounded up to 64 / 128 / 256; finally blocks = ceil(C / cb).
+ * A workgroup of column block j owns input channels j * cb .. min(C, (j + 1) * cb).                                           */
+int sy11_dgrad_wgrad_1x1_plan(int32_t C, int32_t N, int64_t lds_bytes, int32_t* np, int32_t* cp, int32_t* cb, int32_t* blocks);
 
 /* wt[c][t][n] = w[n][t][c]  (t = r*KW+s), same dtype; feeds sy11_conv2d_dgrad                               */
 int sy11_weight_transpose(int32_t dtype, int32_t N, int32_t T, int32_t C, const void* w, void* wt, void* stream);

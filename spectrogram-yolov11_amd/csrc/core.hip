@@ -19,7 +19,7 @@ extern "C" const char* sy11_last_error(void) { return g_err; }
 // ------------------------------------------------------------------------------------------------ run-time options
 static int g_opt[OPT_COUNT];
 static std::once_flag g_opt_once;
-static const char* const kOptName[OPT_COUNT] = {"tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo", "row_map", "deterministic", "maxpool_sep"};
+static const char* const kOptName[OPT_COUNT] = {"tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo", "row_map", "deterministic", "maxpool_sep", "dwgrad_wg", "dwgrad_fused"};
 static void opt_init() {
   auto env = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
   g_opt[OPT_TUNE] = env("SY11_TUNE", 1) != 0;
@@ -33,6 +33,8 @@ static void opt_init() {
   g_opt[OPT_ROW_MAP] = env("SY11_ROW_MAP", 1);
   g_opt[OPT_DETERMINISTIC] = env("SY11_DETERMINISTIC", 0) != 0;
   g_opt[OPT_MAXPOOL_SEP] = env("SY11_MAXPOOL_SEP", 1);
+  g_opt[OPT_DWGRAD_WG] = env("SY11_DWGRAD_WG", 0);
+  g_opt[OPT_DWGRAD_FUSED] = env("SY11_DWGRAD_FUSED", 1) != 0;
 }
 int sy11_opt(int which) {
   std::call_once(g_opt_once, opt_init);
@@ -57,7 +59,7 @@ static int opt_index(const char* name) {
 extern "C" int sy11_set_option(const char* name, int32_t value) {
   const int i = opt_index(name);
   SY11_REQUIRE(last_cfg_index(name) < 0, "set_option: '%s' is read-only (the configuration of the last launch)", name);
-  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic, maxpool_sep; read-only: igemm_last_cfg, wgrad_last_cfg, stem_fwd_last, stem_wgrad_last, pool_fwd_last, pool_bwd_last, ew_vec_last)", name ? name : "(null)");
+  SY11_REQUIRE(i >= 0, "set_option: unknown option '%s' (tune, tune_log, igemm_cfg, wgrad_cfg, igemm_korder, igemm_deep, igemm_bpol, dgrad_s2_halo, row_map, deterministic, maxpool_sep, dwgrad_wg, dwgrad_fused; read-only: igemm_last_cfg, wgrad_last_cfg, stem_fwd_last, stem_wgrad_last, pool_fwd_last, pool_bwd_last, ew_vec_last)", name ? name : "(null)");
   std::call_once(g_opt_once, opt_init);
   g_opt[i] = value;
   return SY11_OK;

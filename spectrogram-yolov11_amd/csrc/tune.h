@@ -21,7 +21,7 @@ constexpr int SY11_WGRAD_NCFG = 20;
 
 // process-wide options (core.hip): defaults come from the environment (SY11_TUNE, SY11_TUNE_LOG, SY11_IGEMM_CFG,
 // SY11_WGRAD_CFG, SY11_IGEMM_KORDER, SY11_IGEMM_DEEP, SY11_IGEMM_BPOL, SY11_MAXPOOL_SEP), sy11_set_option() changes them at run time
-enum Sy11Opt { OPT_TUNE = 0, OPT_TUNE_LOG, OPT_IGEMM_CFG, OPT_WGRAD_CFG, OPT_IGEMM_KORDER, OPT_IGEMM_DEEP, OPT_IGEMM_BPOL, OPT_DGRAD_S2_HALO, OPT_ROW_MAP, OPT_DETERMINISTIC, OPT_MAXPOOL_SEP, OPT_COUNT };
+enum Sy11Opt { OPT_TUNE = 0, OPT_TUNE_LOG, OPT_IGEMM_CFG, OPT_WGRAD_CFG, OPT_IGEMM_KORDER, OPT_IGEMM_DEEP, OPT_IGEMM_BPOL, OPT_DGRAD_S2_HALO, OPT_ROW_MAP, OPT_DETERMINISTIC, OPT_MAXPOOL_SEP, OPT_DWGRAD_WG, OPT_DWGRAD_FUSED, OPT_COUNT };
 int sy11_opt(int which);
 // the configuration of the most recent launch of each table (core.hip), read-only through sy11_get_option as "igemm_last_cfg" /
 // "wgrad_last_cfg"; -1 before the first launch.  One host-side int store per launch: tests read back which kernel they checked.
@@ -30,6 +30,10 @@ constexpr int SY11_CFG_HALO_DGRAD_S2 = 100;
 // The grouped filter-gradient launch (wgrad.hip wgrad16g_kernel, sy11_conv2d_wgrad_group) is no entry of the wgrad table either (it
 // cannot be forced or imported): "wgrad_last_cfg" reads this value after it.
 constexpr int SY11_CFG_WGRAD_GROUP = 100;
+// The fused input + filter gradient of a 1x1 layer (dwgrad1x1.hip, sy11_conv2d_dgrad_wgrad_1x1) records this value as "wgrad_last_cfg".
+// "dwgrad_wg" (SY11_DWGRAD_WG): workgroups per column block of that launch, 0 = one resident round (occupancy API).
+// "dwgrad_fused" (SY11_DWGRAD_FUSED, default 1): the engine's switch — 0 keeps every layer on the pair; the entry point itself ignores it.
+constexpr int SY11_CFG_DWGRAD_1X1 = 101;
 void sy11_note_cfg(int kind, int cfg);     // kind 0 = igemm (fwd / dgrad), 1 = wgrad, 2 = stem forward, 3 = stem filter gradient,
                                             // 4 = 5x5 pool forward, 5 = 5x5 pool backward, 6 = channel-vector width of a data-movement launch
 constexpr int SY11_NOTE_KINDS = 7;

@@ -28,6 +28,7 @@ class ConvDesc(C.Structure):
 
 WGRAD_GROUP_MAX = 32          # SY11_WGRAD_GROUP_MAX
 CFG_WGRAD_GROUP = 100         # "wgrad_last_cfg" after a grouped launch (csrc/tune.h SY11_CFG_WGRAD_GROUP)
+CFG_DWGRAD_1X1 = 101          # ... after the fused input + filter gradient of a 1x1 layer (SY11_CFG_DWGRAD_1X1)
 
 
 class WgradProblem(C.Structure):
@@ -94,6 +95,8 @@ SIGNATURES = {
     "sy11_conv2d_wgrad": [_dp, _vp, _vp, _i32, _vp, _vp],
     "sy11_conv2d_wgrad_group": [_i32, _i32, C.POINTER(WgradProblem), _i32, _vp],
     "sy11_wgrad_group_plan": [_i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_i32)],
+    "sy11_conv2d_dgrad_wgrad_1x1": [_i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
+    "sy11_dgrad_wgrad_1x1_plan": [_i32, _i32, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
     "sy11_weight_transpose": [_i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "sy11_weight_transpose_multi": [_i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "sy11_stem_conv_fwd": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -267,7 +270,7 @@ def call(name: str, *args):
 
 def set_option(name: str, value: int):
     """sy11_set_option: "tune", "tune_log", "igemm_cfg", "wgrad_cfg", "igemm_korder", "igemm_deep", "igemm_bpol", "dgrad_s2_halo",
-    "row_map", "deterministic", "maxpool_sep".  "igemm_last_cfg" / "wgrad_last_cfg" / "stem_fwd_last" / "stem_wgrad_last" /
+    "row_map", "deterministic", "maxpool_sep", "dwgrad_fused", "dwgrad_wg".  "igemm_last_cfg" / "wgrad_last_cfg" / "stem_fwd_last" / "stem_wgrad_last" /
     "pool_fwd_last" / "pool_bwd_last" / "ew_vec_last" are read-only (get_option) and refused here."""
     check(load().sy11_set_option(name.encode(), int(value)), "sy11_set_option")
 

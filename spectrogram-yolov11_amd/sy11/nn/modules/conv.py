@@ -20,6 +20,22 @@ import os
 _BN_TAIL = os.environ.get("SY11_BN_TAIL", "0") != "0"
 _BN_STAT_SLOTS = max(1, int(os.environ.get("SY11_BN_STAT_SLOTS", "32")))     # statistic rows per layer; r04 sweep: 4 ... 32 rows are equal within noise, 1 row costs 0.65 ms per step (profiles/r04/bn_fused_finalize_experiment.txt)
 
+# Large-map dense 1x1 layers: input gradient and filter gradient in ONE launch that reads dy once (ops.conv2d_dgrad_wgrad_1x1,
+# csrc/dwgrad1x1.hip) instead of conv2d_dgrad on the main stream plus conv2d_wgrad on the side stream.  M = B * H * W pixels at
+# least; the option "dwgrad_fused" (SY11_DWGRAD_FUSED, default 1) turns it off.  The threshold: DESIGN.md section 6, round 6.
+_DWGRAD_FUSED_MIN_PIXELS = 409600
+
+
+def fused_dwgrad_applies(k, s, g, d, dtype, M, det, padded, C=16, N=16, threshold=None) -> bool:
+    """The dispatch rule of the fused 1x1 backward, a pure function: dense 1x1 stride 1 (hole-free by construction), a 16-bit
+    dtype, channels the kernel takes, not the zero-padded-channel path, ordered mode off, at least ``threshold`` pixels."""
+    if threshold is None:
+        threshold = _DWGRAD_FUSED_MIN_PIXELS
+    return (k == 1 and s == 1 and g == 1 and d == 1 and dtype in (torch.float16, torch.bfloat16) and not padded and not det
+            and C % 16 == 0 and N % 16 == 0 and 16 <= C <= 256 and 16 <= N <= 256 and M >= threshold
+            and not ops.dgrad_leaves_holes(k, s, 0, d))
+
+
 __all__ = ("Conv", "DWConv", "DDWConv", "Concat", "WeightedSpatialAttention", "GCT", "Fusion", "autopad")
 
 
@@ -229,6 +245,12 @@ class Conv(nn.Module):
                 ops.bn_act_bwd_apply(y, dz, mean, rstd, scale, shift, gamma, silu, sg[0], sg[1], dy,
                                      gs.grad_vec(bn.weight) if has_bn else None, gs.grad_vec(bn.bias) if has_bn else None,
                                      res_grad=rg, res_accumulate=acc)
+                if (not stem and x.req and p == 0 and id(conv.weight) in gs.views
+                        and fused_dwgrad_applies(k, s, g, d, ec.dtype, B * OH * OW, ops._lib.get_option("deterministic") != 0, padded, C1, N)
+                        and ops._lib.get_option("dwgrad_fused") != 0):
+                    gx, acc = x.grad_for_write()
+                    ops.conv2d_dgrad_wgrad_1x1(dy, x.data, ec.transposed(conv.weight, w), gx, gs.grad_krsc(conv.weight), accumulate=acc)
+                    return
                 if id(conv.weight) in gs.views:
                     dw = gs.grad_krsc(conv.weight)
                     if stem:

@@ -158,6 +158,37 @@ def conv2d_wgrad(x, dy, dw_f32, k, s=1, p=0, d=1, groups=1):
     return dw_f32
 
 
+def conv2d_dgrad_wgrad_1x1(dy, x, wt, dx, dw_f32, accumulate=False):
+    """Dense 1x1 / stride-1 layer: dx (NHWC view, the shape of x) = dy * w [+ dx] AND dw_f32 ([N][1][1][C], f32) += dy^T * x in one
+    launch that reads dy once (sy11_conv2d_dgrad_wgrad_1x1).  dy, x, dx: 16-bit NHWC views of the same B, H, W; wt: the
+    tap-transposed filter [C][1][1][N] of weight_transpose."""
+    _need_gpu(dy, x, wt, dx, dw_f32)
+    B, H, W, N = dy.shape
+    Cn = x.shape[3]
+    if tuple(x.shape[:3]) != (B, H, W) or tuple(dx.shape) != tuple(x.shape) or x.dtype != dy.dtype or dx.dtype != dy.dtype or wt.dtype != dy.dtype:
+        raise _lib.Sy11Error(f"conv2d_dgrad_wgrad_1x1: dy {tuple(dy.shape)} {dy.dtype}, x {tuple(x.shape)} {x.dtype}, dx {tuple(dx.shape)} {dx.dtype} "
+                             f"do not belong to one 1x1 stride-1 layer")
+    if dw_f32.dtype != torch.float32 or not dw_f32.is_contiguous() or dw_f32.numel() != N * Cn:
+        raise _lib.Sy11Error("conv2d_dgrad_wgrad_1x1: dw must be a contiguous f32 tensor of N * C elements")
+    if not wt.is_contiguous() or wt.numel() != N * Cn:
+        raise _lib.Sy11Error("conv2d_dgrad_wgrad_1x1: wt must be the contiguous [C][1][1][N] filter of weight_transpose")
+    M = B * H * W
+    if _lib.PROFILE is not None:     # both GEMMs; dy, x and dx once each, the filter read and its gradient written
+        es = dy.element_size()
+        _lib.PROFILE_META = {"flops": 4.0 * M * N * Cn, "groups": 1, "bytes": (M * N + 2 * M * Cn + 2 * N * Cn) * es,
+                             "desc": f"B{B} {H}x{W}x{Cn}->{H}x{W}x{N} k1 s1 g1 dgrad+wgrad"}
+    call("sy11_conv2d_dgrad_wgrad_1x1", dt_code(dy.dtype), M, Cn, N, _p(dy), view_ld(dy), _p(x), view_ld(x), _p(wt), _p(dx), view_ld(dx),
+         1 if accumulate else 0, _p(dw_f32), _stream())
+    return dx
+
+
+def dgrad_wgrad_1x1_plan(Cn, N, lds_bytes=160 * 1024):
+    """The tile choice of conv2d_dgrad_wgrad_1x1 (sy11_dgrad_wgrad_1x1_plan, host arithmetic): (np, cp, cb, blocks)."""
+    v = [C.c_int32() for _ in range(4)]
+    _lib.check(_lib.load().sy11_dgrad_wgrad_1x1_plan(int(Cn), int(N), int(lds_bytes), *[C.byref(e) for e in v]), "sy11_dgrad_wgrad_1x1_plan")
+    return tuple(int(e.value) for e in v)
+
+
 def conv2d_wgrad_group(problems, target_workgroups=0):
     """Several dense 16-bit filter gradients in one launch (sy11_conv2d_wgrad_group): ``problems`` is a sequence of
     (x, dy, dw_f32, k, s, p, d), each exactly conv2d_wgrad(x, dy, dw_f32, k, s, p, d).  A list longer than WGRAD_GROUP_MAX goes out
