@@ -834,6 +834,93 @@ int sy11_fsk_symbols(int32_t n_item, const sy11_fsk_block* item_host, const sy11
 int sy11_fsk_decide(int32_t n_item, const sy11_fsk_dec* item_host, const sy11_fsk_dec* item, int64_t n_sym, const float* sym, float* r,
                     uint8_t* d, int64_t n_rows, double* rows, void* stream);
 
+/* ---- OFDM demodulation: cyclic-prefix OFDM clips of an extraction with fixed, uniformly spaced pilots (spec in DESIGN.md §4) ----
+ * Feed-forward, three launches over all clips; the two fits between them are the caller's (sy11/data/demodulate_ofdm.py).  The result has the
+ * shape of the demodulation's: the data carriers of every OFDM symbol, one after the other, as corrected symbols and decisions.  A clip has an
+ * FFT size N = n_fft in {64, 128, 256, 512, 1024}, a prefix of G samples (1 <= G <= N / 2), a period S = N + G and Lp = (len - N) / S whole periods;
+ * the clips of one call may differ in all of them.
+ *
+ * Launch 1, sy11_iq_ofdm_fold.  An item is a tile of 64 residues [r0  r0 + cnt_r) of the period (r0 a multiple of 64, cnt_r = min(64, S - r0)) and
+ * a split of 16 periods [m0  m0 + cnt_m) of the clip (m0 a multiple of 16, cnt_m = 16 except on the clip's last split).  Per residue r, in float64,
+ * the periods in ascending order (the products of two float32 values are exact):
+ *   F = sum_m in[r + m S + N] conj(in[r + m S])     E = sum_m (|in[r + m S]|^2 + |in[r + m S + N]|^2) / 2     out[3 (out_off + r - r0) + 0 .. 2] = Re F, Im F, E
+ * item: DEVICE table, item_host: its HOST copy, checked entry by entry before anything is launched: n_fft is in the set, the clip lies inside
+ * in[0  n_in), the residues are a tile and the periods a split of the clip's, and every triple of out[0  3 n_out) is written by one item.
+ * in: packed complex64 (a clip may start at an odd sample).  No atomics.  Nothing is launched on an error.
+ *
+ * Launch 2, sy11_ofdm_fft.  An item is 1 .. 1024 / N consecutive OFDM symbols of one clip; symbol f of the item transforms the N samples from
+ * start + f S of the clip:  v[q] = in[n] e^{-2 pi i (n w mod 2^64) 2^-64} (n = start + f S + q, float64),  Y[k] = (sum_q v[q] e^{-2 pi i k q / N}) e^{+2 pi i k a / N}
+ * (the advance turn is entry (k a) mod N of the twiddle table: exact).  The item's carriers are bin[bin_off  bin_off + n_used): signed k in
+ * (-N / 2, N / 2), ascending; pil = 0 for a data carrier, +-(p + 1) for pilot p of n_pil with the value +-1.  Per symbol f and carrier j:
+ *   yc[2 (yc_off + f n_used + j)] = f32(Y[k_j]) (rounded ONCE)     pil[2 (pil_off + f n_pil + p)] = +-Y[k_j] (float64)     pw[pow_off + f] = sum_j |Y[k_j]|^2 (float64)
+ * twiddle: e^{-2 pi i m / 1024}, m < 512, as (Re, Im) float64 pairs, 16-byte aligned: the table of every N is a stride of it.  Checked: n_fft in the set,
+ * S and a fit it, the symbols lie inside the clip and the clip inside in[0  n_in), the carriers are ascending and inside (-N / 2, N / 2) and name
+ * every pilot once, and every entry of yc, pil and pw is written by one item.
+ *
+ * Launch 3, sy11_ofdm_decide.  An item is one OFDM symbol: its n_used carrier values yc[yc_off ..] and its n_data data carriers
+ * car[car_off  car_off + n_data), each the index idx of its value among the used ones and its turn tau = (tr, ti).  In float64, rounded ONCE:
+ *   r_j = f32((yc[yc_off + idx_j] rho) tau_j) -> r[2 (sym_off + j)]     d[sym_off + j] as sy11_demod_decide at the item's order     rows[row 3 + 0 .. 2] = sum |r|^2, sum Re(r conj(point(d))), n_data
+ * Checked: the values inside yc[0  n_yc), the symbols inside r / d (n_sym entries) and written by one item, idx < n_used, rho and every tau finite,
+ * order 2 or 4, one item per row.                                                                                                  */
+typedef struct sy11_ofdm_fold_item {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip                                                              */
+  int64_t out_off;             /* the triple of residue r0 in the item's partial row                               */
+  int32_t n_fft;               /* N                                                                                */
+  int32_t S;                   /* the period, N + G                                                                */
+  int32_t r0;                  /* first residue of the tile, a multiple of 64                                      */
+  int32_t cnt_r;               /* residues of the tile, min(64, S - r0)                                            */
+  int32_t m0;                  /* first period of the split, a multiple of 16                                      */
+  int32_t cnt_m;               /* periods of the split, 1 .. 16                                                    */
+} sy11_ofdm_fold_item;
+typedef struct sy11_ofdm_bin {
+  int32_t k;                   /* signed carrier index, -N / 2 < k < N / 2                                         */
+  int32_t pil;                 /* 0: a data carrier; +-(p + 1): pilot p with the value +-1                         */
+} sy11_ofdm_bin;
+typedef struct sy11_ofdm_fft_item {
+  int64_t off;                 /* first sample of the clip in the packed buffer                                    */
+  int64_t len;                 /* samples of the clip                                                              */
+  int64_t start;               /* first sample of the item's first FFT window (index in the clip)                  */
+  uint64_t w;                  /* carrier: cycles per sample 2^64, wrapping                                        */
+  int64_t yc_off;              /* the item's first carrier value in yc (complex64 entries)                         */
+  int64_t pil_off;             /* the item's first pilot value in pil (complex128 entries)                         */
+  int64_t pow_off;             /* the item's first power row                                                       */
+  int32_t n_fft;               /* N                                                                                */
+  int32_t S;                   /* the period, N + G                                                                */
+  int32_t a;                   /* the advance: samples the window starts inside the prefix, 0 .. G                 */
+  int32_t nf;                  /* OFDM symbols of the item, 1 .. 1024 / N                                          */
+  int32_t bin_off;             /* the clip's first carrier in the carrier table                                    */
+  int32_t n_used;              /* its carriers, data and pilots, 1 .. N - 1                                        */
+  int32_t n_pil;               /* its pilots, 1 .. n_used                                                          */
+  int32_t reserved;
+} sy11_ofdm_fft_item;
+typedef struct sy11_ofdm_car {
+  int32_t idx;                 /* the data carrier's place among the used carriers                                 */
+  int32_t reserved;
+  double tr;                   /* its turn tau, real part                                                          */
+  double ti;                   /* and imaginary part                                                               */
+} sy11_ofdm_car;
+typedef struct sy11_ofdm_dec {
+  int64_t yc_off;              /* the OFDM symbol's first carrier value in yc                                      */
+  int64_t sym_off;             /* its first symbol in the packed symbol buffer                                     */
+  double rho_r;                /* the symbol's correction rho, real part                                           */
+  double rho_i;                /* and imaginary part                                                               */
+  int32_t car_off;             /* the clip's first data carrier in the carrier table                               */
+  int32_t n_data;              /* its data carriers, 1 .. n_used                                                   */
+  int32_t n_used;              /* its used carriers, 1 .. 1023                                                     */
+  int32_t order;               /* 2 or 4                                                                           */
+  int32_t row;                 /* row of the table the item writes                                                 */
+  int32_t reserved;
+} sy11_ofdm_dec;
+int sy11_iq_ofdm_fold(int32_t n_item, const sy11_ofdm_fold_item* item_host, const sy11_ofdm_fold_item* item, int64_t n_in, const float* in,
+                      int64_t n_out, double* out, void* stream);
+int sy11_ofdm_fft(int32_t n_item, const sy11_ofdm_fft_item* item_host, const sy11_ofdm_fft_item* item, int32_t n_bin, const sy11_ofdm_bin* bin_host,
+                  const sy11_ofdm_bin* bin, const double* twiddle, int64_t n_in, const float* in, int64_t n_yc, float* yc, int64_t n_pil, double* pil,
+                  int64_t n_pow, double* pw, void* stream);
+int sy11_ofdm_decide(int32_t n_item, const sy11_ofdm_dec* item_host, const sy11_ofdm_dec* item, int32_t n_car, const sy11_ofdm_car* car_host,
+                     const sy11_ofdm_car* car, int64_t n_yc, const float* yc, int64_t n_sym, float* r, uint8_t* d, int64_t n_rows, double* rows,
+                     void* stream);
+
 /* ---- frame search: where the sync words sit in the corrected symbols of every clip, and at which rotation (spec in DESIGN.md §4) ----
  * Three launches over all clips; between the second and the third the caller compacts the hits (sy11/data/frames.py).  sym: the packed
  * corrected symbols (complex64, what sy11_demod_decide wrote to r); words: packed DECISIONS of the words, one byte per symbol as d of

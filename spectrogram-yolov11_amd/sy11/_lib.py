@@ -163,6 +163,9 @@ SIGNATURES = {
     "sy11_iq_fsk_filter": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "sy11_fsk_symbols": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "sy11_fsk_decide": [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp],
+    "sy11_iq_ofdm_fold": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "sy11_ofdm_fft": [_i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "sy11_ofdm_decide": [_i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "sy11_sync_correlate": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "sy11_sync_peaks": [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp],
     "sy11_sync_frames": [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],

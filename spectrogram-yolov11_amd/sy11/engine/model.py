@@ -374,6 +374,13 @@ class YOLO:
         from ..data.demodulate_fsk import demodulate_fsk_extraction
         return demodulate_fsk_extraction(extraction, symbol_rate=symbol_rate, offset=offset, pulse=pulse, bt=bt, span=span, block=block)
 
+    def demodulate_ofdm(self, extraction, *, n_fft, cp, carriers, pilots, order=4, offset=0.0, spacing=None, advance=None):
+        """Demodulate every cyclic-prefix OFDM clip of ``extraction`` on the GPU -> ``sy11.data.demodulate_ofdm.OfdmDemodulation``: a ``Demodulation`` at the clips' ``order``
+        with the data carriers of every OFDM symbol as corrected symbols and decisions, the error-vector magnitude, where the prefix starts and the carrier
+        offset, from the caller's layout (``n_fft``, ``cp``, ``carriers``, ``pilots``) (``DetectionPredictor.demodulate_ofdm``)."""
+        from ..data.demodulate_ofdm import demodulate_ofdm_extraction
+        return demodulate_ofdm_extraction(extraction, n_fft=n_fft, cp=cp, carriers=carriers, pilots=pilots, order=order, offset=offset, spacing=spacing, advance=advance)
+
     def find_frames(self, demodulation, words, *, payload=0, threshold=0.8, max_errors=None, t0=None):
         """Find the sync ``words`` in every clip of ``demodulation`` on the GPU -> ``sy11.data.frames.Frames``: per frame its clip, word, position, the
         rotation that resolves the demodulator's phase ambiguity, the word's errors and ``payload`` symbols' bits

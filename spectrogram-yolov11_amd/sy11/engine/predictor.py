@@ -323,6 +323,23 @@ class DetectionPredictor:
         from ..data.demodulate_fsk import demodulate_fsk_extraction
         return demodulate_fsk_extraction(extraction, symbol_rate=symbol_rate, offset=offset, pulse=pulse, bt=bt, span=span, block=block)
 
+    def demodulate_ofdm(self, extraction, *, n_fft, cp, carriers, pilots, order=4, offset=0.0, spacing=None, advance=None):
+        """Read every cyclic-prefix OFDM clip of ``extraction`` (what ``extract`` returned) -> ``sy11.data.demodulate_ofdm.OfdmDemodulation``, a ``Demodulation`` at the clips'
+        ``order`` that ``find_frames``, ``equalize``, ``decode``, ``decode_ldpc`` and ``correct`` take as it is (``csrc/demod_ofdm.hip``).  The clip must be sampled at ``n_fft`` carrier
+        spacings (a capture at another rate goes through the resampler in front of the scan, or through ``extract(decimate=)``); ``cp`` is the prefix in samples, ``carriers`` the
+        data carriers (signed), ``pilots`` a mapping k -> +-1 or a pair ``(k_p, c_p)``: at least 2, uniformly spaced, the same in every OFDM symbol.  ``order`` (2 or 4) and ``offset``
+        (Hz from the clip's centre, right to within half a carrier spacing) are per clip or scalars; ``n_fft``, ``cp``, ``carriers``, ``pilots`` and ``advance`` may be given per clip as
+        lists.  All clips go through THREE launches: the prefix correlation ``x[n + n_fft] conj(x[n])`` folded over the period, whose peak gives where the OFDM symbols start
+        (``timing``) and the fractional carrier offset (``cfo``, ``carrier_fit``, ``cp_corr``); the FFT of every OFDM symbol, its window started ``advance`` samples inside the prefix,
+        with the pilots' values and the power; the data carriers turned by the pilots' common phase and slope (``slope``) and scaled by their amplitude, and the decisions.  OFDM symbols
+        whose pilots are weaker than half the strongest are not ``active``: they stay in ``symbols`` so that a position maps to a time, and stay out of ``gain``, ``evm`` and ``mer_db``.
+        The pilots fix the phase (``phase_ambiguity`` 1).  A clip that cannot be demodulated (order, ``spacing`` against the clip's rate, |offset| >= fs / 2, fewer than 2 whole periods)
+        is a row with ``valid`` False and a ``reason``.  Not done here: pilots that change from symbol to symbol, non-uniform pilots, a per-carrier channel estimate, a search over
+        whole carrier spacings, sampling-clock offset, 16-QAM and above, interleaver and scrambler, n_fft above 1024.  Argument errors are ``ValueError``s raised before anything
+        touches the device; without a valid clip nothing is launched."""
+        from ..data.demodulate_ofdm import demodulate_ofdm_extraction
+        return demodulate_ofdm_extraction(extraction, n_fft=n_fft, cp=cp, carriers=carriers, pilots=pilots, order=order, offset=offset, spacing=spacing, advance=advance)
+
     def find_frames(self, demodulation, words, *, payload=0, threshold=0.8, max_errors=None, t0=None):
         """Say where framed data starts in every clip of ``demodulation`` (what ``demodulate`` returned) and at which of the ``order`` rotations the
         demodulator landed -> ``sy11.data.frames.Frames``, one row per frame sorted by (clip, word, position) (``csrc/framesync.hip``).  ``words``: the

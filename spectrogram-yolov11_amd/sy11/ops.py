@@ -1250,6 +1250,92 @@ def fsk_decide(sym, items, r, d, rows):
     return r, d, rows
 
 
+def _records(what, name, v, dtype):
+    """``v`` as a non-empty contiguous 1-D array of ``dtype`` records; a ``ValueError`` otherwise."""
+    it = np.ascontiguousarray(v)
+    if it.dtype != dtype or it.ndim != 1 or it.shape[0] == 0 or it.shape[0] >= 2 ** 31:
+        raise ValueError(f"{what}: `{name}` must be a non-empty 1-D array of sy11.data.demodulate_ofdm records {tuple(dtype.names)}")
+    return it
+
+
+def _flat(what, name, v, dtype, dev, like=None):
+    if v.dtype != dtype or v.dim() != 1 or not v.is_contiguous() or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or v.device != dev or v.data_ptr() % 8 \
+            or (like is not None and v.shape != like.shape):
+        raise _lib.Sy11Error(f"{what}: `{name}` must be a non-empty 1-D contiguous 8-byte aligned {dtype} tensor below 2^31 on the input's device"
+                             + ("" if like is None else f" of {like.shape[0]} entries"))
+
+
+def iq_ofdm_fold(x, items, out):
+    """Launch 1 of the OFDM demodulation (sy11_iq_ofdm_fold): every item of ``items`` — ``sy11.data.demodulate_ofdm.FOLD`` records (off, len, out_off, n_fft, S, r0, cnt_r, m0,
+    cnt_m): the residues ``[r0, r0 + cnt_r)`` of the period ``S`` and the periods ``[m0, m0 + cnt_m)`` of the clip ``x[off : off + len]`` — writes per residue the sums of
+    ``x[n + n_fft] conj(x[n])`` (Re, Im) and of the mean energy of the two samples to ``out[out_off + r - r0]`` (triples, 3) f64.  ``x``: the packed clips, 1-D contiguous
+    complex64.  A table that is not one of ``FOLD`` records is a ``ValueError``; a call the library refuses raises ``Sy11Error`` and writes nothing.  -> ``out``."""
+    from .data.demodulate_ofdm import FOLD
+    what = "iq_ofdm_fold"
+    _need_gpu(x, out)
+    _packed_c64(what, "x", x)
+    _rows_of(what, "out", out, x.device, 3)
+    it = _records(what, "items", items, FOLD)
+    t = torch.from_numpy(it.view(np.uint8)).to(x.device)
+    call("sy11_iq_ofdm_fold", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), x.shape[0], C.c_void_p(torch.view_as_real(x).data_ptr()), out.shape[0],
+         _p(out), _stream())
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return out
+
+
+def ofdm_fft(x, items, bins, twiddle, yc, pilots, power):
+    """Launch 2 of the OFDM demodulation (sy11_ofdm_fft): every item of ``items`` — ``sy11.data.demodulate_ofdm.FFT`` records (off, len, start, w, yc_off, pil_off, pow_off, n_fft,
+    S, a, nf, bin_off, n_used, n_pil): ``nf`` (1 .. 1024 / n_fft) OFDM symbols of the clip ``x[off : off + len]``, the first FFT window at ``start`` — turns the samples back by
+    ``w``, transforms them, turns carrier k by ``e^{2 pi i k a / n_fft}`` and writes, per OFDM symbol, the carriers ``bins[bin_off : bin_off + n_used]`` (``BIN`` records: k, pil) to
+    ``yc`` (complex64), the pilots times their values to ``pilots`` (complex128) and the power of the used carriers to ``power`` (float64).  ``twiddle``: (512, 2) float64,
+    ``e^{-2 pi i m / 1024}``.  A table that is not one of its records is a ``ValueError``; a call the library refuses raises ``Sy11Error`` and writes nothing.  -> the device copy of
+    ``bins``."""
+    from .data.demodulate_ofdm import BIN, FFT
+    what = "ofdm_fft"
+    _need_gpu(x, twiddle, yc, pilots, power)
+    _packed_c64(what, "x", x)
+    dev = x.device
+    _flat(what, "yc", yc, torch.complex64, dev)
+    _flat(what, "pilots", pilots, torch.complex128, dev)
+    _flat(what, "power", power, torch.float64, dev)
+    if twiddle.dtype != torch.float64 or tuple(twiddle.shape) != (512, 2) or not twiddle.is_contiguous() or twiddle.device != dev or twiddle.data_ptr() % 16 or pilots.data_ptr() % 16:
+        raise _lib.Sy11Error(f"{what}: `twiddle` must be a contiguous (512, 2) float64 tensor on the input's device; it and `pilots` 16-byte aligned")
+    it, bn = _records(what, "items", items, FFT), _records(what, "bins", bins, BIN)
+    t, b = torch.from_numpy(it.view(np.uint8)).to(dev), torch.from_numpy(bn.view(np.uint8)).to(dev)
+    call("sy11_ofdm_fft", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), bn.shape[0], C.c_void_p(bn.ctypes.data), C.c_void_p(b.data_ptr()), _p(twiddle),
+         x.shape[0], C.c_void_p(torch.view_as_real(x).data_ptr()), yc.shape[0], C.c_void_p(torch.view_as_real(yc).data_ptr()), pilots.shape[0],
+         C.c_void_p(torch.view_as_real(pilots).data_ptr()), power.shape[0], _p(power), _stream())
+    for v in (t, b):
+        v.record_stream(torch.cuda.current_stream(dev))
+    return b
+
+
+def ofdm_decide(yc, items, cars, r, d, rows):
+    """Launch 3 of the OFDM demodulation (sy11_ofdm_decide): every item of ``items`` — ``sy11.data.demodulate_ofdm.DEC`` records (yc_off, sym_off, rho_r, rho_i, car_off, n_data,
+    n_used, order, row): one OFDM symbol, its ``n_used`` carrier values from ``yc[yc_off]`` — writes ``(yc[yc_off + idx] rho) tau`` for the data carriers
+    ``cars[car_off : car_off + n_data]`` (``CAR`` records: idx, tr, ti) to ``r[sym_off ..]`` (complex64), the decisions at ``order`` to ``d`` (uint8) and the sums of ``|r|^2``,
+    ``Re(r conj(point(d)))`` and the count to ``rows[row]`` (rows, 3) f64.  A table that is not one of its records is a ``ValueError``; a call the library refuses (a turn that is
+    not finite among them) raises ``Sy11Error`` and writes nothing.  -> the device copy of ``cars``."""
+    from .data.demodulate_ofdm import CAR, DEC
+    what = "ofdm_decide"
+    _need_gpu(yc, r, d, rows)
+    dev = yc.device
+    _flat(what, "yc", yc, torch.complex64, dev)
+    _flat(what, "r", r, torch.complex64, dev)
+    if d.dtype != torch.uint8 or tuple(d.shape) != tuple(r.shape) or not d.is_contiguous() or d.device != dev:
+        raise _lib.Sy11Error(f"{what}: `d` must be a contiguous ({r.shape[0]},) uint8 tensor on yc's device")
+    _row_table(what, "rows", rows, dev)
+    if r.data_ptr() == yc.data_ptr():
+        raise _lib.Sy11Error(f"{what}: `r` may not be yc")
+    it, cr = _records(what, "items", items, DEC), _records(what, "cars", cars, CAR)
+    t, c = torch.from_numpy(it.view(np.uint8)).to(dev), torch.from_numpy(cr.view(np.uint8)).to(dev)
+    call("sy11_ofdm_decide", it.shape[0], C.c_void_p(it.ctypes.data), C.c_void_p(t.data_ptr()), cr.shape[0], C.c_void_p(cr.ctypes.data), C.c_void_p(c.data_ptr()), yc.shape[0],
+         C.c_void_p(torch.view_as_real(yc).data_ptr()), r.shape[0], C.c_void_p(torch.view_as_real(r).data_ptr()), _p(d), rows.shape[0], _p(rows), _stream())
+    for v in (t, c):
+        v.record_stream(torch.cuda.current_stream(dev))
+    return c
+
+
 def _u8_vector(what, name, v, dev, n=None, exc=_lib.Sy11Error):
     if v.dtype != torch.uint8 or v.dim() != 1 or v.shape[0] == 0 or v.shape[0] >= 2 ** 31 or not v.is_contiguous() or v.device != dev \
             or (n is not None and v.shape[0] != n):
